@@ -18,10 +18,20 @@ of a 32-byte record per rank, reduced on the device). Consecutive steps are inde
 batches and alternate over --streams (default 2) HIP streams, each with its own job, so one
 batch's argmin tail and launch gap hide under the next batch's scoring.
 
-Printed (rank 0): one JSON line with value = candidates scored per second over all ranks,
-a `roofline` object for the dominant kernel (k_sspp_c2f), a `binding_roofline` (FP64 VALU) object, and a
-`cpu_baseline` object (the oracle — test infrastructure, oracle/ — timed on a bounded sample
-of the same workload on the host cores, N=1 only, with a parity check on that sample).
+Printed (rank 0): one JSON line with value = candidates scored per second over all ranks and
+ms_per_step = milliseconds per timed step.  A plain run sets up, warms up, times --steps steps
+and prints the line.  With --full the line also carries a `roofline` object for the dominant
+kernel (k_sspp_c2f), a `binding_roofline` (FP64 VALU) object, and a `cpu_baseline` object (the
+oracle — test infrastructure, oracle/ — timed on a bounded sample of the same workload on the
+host cores, N=1 only, with a parity check on that sample), the isolated single-batch latency
+and the scan-order A/B; each of these takes launches or host runs of its own after the timed
+region.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step computed (the arrays
+a caller of the timed path receives: per-candidate results and the argmin record, or every
+goal's CES iteration) as DIR/<name>.npy in float32 / float64, finite values only (a colliding
+candidate's +inf cost is written as 0 and marked in DIR/<name>_nonfinite.npy).  The candidates are counter-based
+Philox draws of a fixed seed, so the same arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -52,7 +62,14 @@ def parse(argv=None):
     ap.add_argument("--config", default="robocrane", choices=["robocrane", "stacking", "multigoal"])
     ap.add_argument("--batch", type=int, default=0, help="candidates per GPU per step (default: config)")
     ap.add_argument("--waypoints", type=int, default=128)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: the dominant "
+                         "kernel's roofline launches, the CPU baseline (oracle) with its parity check, "
+                         "the isolated single-batch latency and the scan-order A/B (default: the timed "
+                         "steps and the result line only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32/float64)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget (--full)")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--roofline-launches", type=int, default=200)
@@ -220,7 +237,8 @@ def setup_robocrane(args, device):
     ctx = dict(kind="sspp", kernel_name="k_sspp_c2f", effective=job.config,
                job=job, knots=knots, ctrl0=ctrl0, W=W, scene_path=model.path, p=p,
                make_executor=make_executor, isolated_step_us=isolated_step_us, set_order=set_order,
-               validate=validate, timed_instance=timed_instance, per_launch=B * roofline_spl(args))
+               validate=validate, timed_instance=timed_instance, per_launch=B * roofline_spl(args),
+               lane_outputs=lambda lane: dict(arc=bufs[lane]["arc"], feasible=bufs[lane]["feasible"]))
     return B, step, kernel_only, bytes_per, flops_per, meta, ctx
 
 
@@ -265,7 +283,8 @@ def setup_stacking(args, device):
     ctx = dict(kind="tsp", job=job, start=start, end=end, mean=mean, sigma=sigma, lo=lo, hi=hi,
                cp=cp, scene_path=model.path, body=model.body_id("block1"),
                effective=lambda: dict(tsp_form=int(job.get_option(S.OPT_TSP_FORM)),
-                                      tsp_rep=int(job.get_option(S.OPT_TSP_REP))))
+                                      tsp_rep=int(job.get_option(S.OPT_TSP_REP))),
+               lane_outputs=lambda lane: {k: bufs[lane][k] for k in ("L", "Cnf", "Cwf", "status", "cost")})
     return B, step, kernel_only, bytes_per, flops_per, meta, ctx
 
 
@@ -330,6 +349,16 @@ def setup_multigoal(args, device, world, rank):
         else:
             pls[0].eval(rank=0, stream=torch.cuda.current_stream())
 
+    def outputs():
+        # every goal's last CES iteration as a caller reads it back (CesPlanner.read)
+        out = {}
+        for g, pl in zip(mine, pls):
+            r = pl.read()
+            for k in ("cost", "status", "L", "vias", "mean", "sigma", "last_best"):
+                out["goal%d_%s" % (g, k)] = r[k]
+            out["goal%d_state" % g] = np.array([r["n_candidates"], r["n_success"], r["best_slot"], r["best_cost"]])
+        return out
+
     bytes_per = 3 * 4 * 8 + 8 + 1
     flops_per = (2 * cp + 1) * 2 * 3 * 4 + cp * (3 * 4 + 1) + cp * (40 + 7 * 42 + 48 + 8 * 450)
     meta = dict(workload="robocrane TaskSpacePlanner multi-goal (gripper, 7 geoms), %d goals, "
@@ -338,7 +367,7 @@ def setup_multigoal(args, device, world, rank):
                 candidates_per_goal=samples + 2, waypoints=cp, vias=1, degree=2, dof=4)
     meta["launch_form"] = "k_tsp_group (all goals per iteration)" if args.mg_group else "k_tsp per goal"
     ctx = dict(kind="multigoal", kernel_name="k_tsp_group" if args.mg_group else "k_tsp", run_steps=run_steps,
-               planners=pls, mine=mine,
+               planners=pls, mine=mine, outputs=outputs,
                scene_path=model.path, body=body, cp=cp, samples=samples)
     # candidates per step over ALL ranks: every goal's list (mean set + best + samples)
     return (samples + 2) * len(MULTIGOAL) // max(1, world), None, kernel_only, bytes_per, \
@@ -525,6 +554,7 @@ def native_runner(args, ctx, B, world, rank, device, on_chunk=None):
     best = torch.zeros((G, 4), dtype=torch.int64, device=device)
     gbufs = {}
     counter = [0]
+    last = [0, None]  # the last chunk: its steps and its (global) records
 
     def gbuf(g):
         if g not in gbufs:
@@ -566,8 +596,22 @@ def native_runner(args, ctx, B, world, rank, device, on_chunk=None):
                 rec = gout
             if on_chunk is not None:
                 on_chunk(rec)
+            last[:] = [g, rec]
             counter[0] += g
             k -= g
+
+    def outputs():
+        # the last step run: its launch's branch holds its arc / feasible (steps_per_launch steps
+        # per launch, launch l of a call on branch l % branches), its record closes the chunk's
+        g, rec = last
+        if not g:
+            return {}
+        spl = args.steps_per_launch
+        launch = (g - 1) // spl
+        b, at = launch % ex.nb, (g - 1) - launch * spl
+        return dict(arc=ex.arc_bufs[b][at * B:(at + 1) * B], feasible=ex.feas_bufs[b][at * B:(at + 1) * B],
+                    best=rec[g - 1])
+    run_steps.outputs = outputs
     return run_steps
 
 
@@ -747,7 +791,7 @@ def run_tsp_anytime(args):
         pl.plan(q0, qT, True)
     tight_us = (time.perf_counter() - t0) / 200 * 1e6
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline_anytime(args, model, q0, qT)
     line = {
         "metric": "TaskSpacePlanner.plan(q0, qT, True) latency, ICRA anytime benchmark size",
@@ -790,6 +834,49 @@ def cpu_baseline_anytime(args, model, q0, qT):
                 **cpu_info())
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, outputs):
+    """--dump-outputs: every array of `outputs` (name -> device tensor or host array) as
+    directory/<name>.npy.  Floating-point arrays keep their precision (float64 / float32), integer
+    and flag arrays go to float32 when every value fits its 24-bit mantissa and to float64
+    otherwise; an argmin record (int64[4]: cost bits, id, feasible count, lost-work field) is
+    written as float64 [cost, id, feasible count, lost].  Every written value is finite: where an
+    array holds +inf (a colliding candidate's cost), -inf or NaN, 0 is written in its place and
+    <name>_nonfinite.npy marks the entries (0 finite, 1 +inf, -1 -inf, 2 NaN).  Past 64 MB in all, every array is cut
+    down to a fixed seeded sample of its flattened entries (the same entries in every run)."""
+    arrays = {}
+    for name, a in outputs.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        if name == "best":
+            a = np.concatenate([a[:1].view(np.float64), a[1:].astype(np.float64)])
+        elif a.dtype not in (np.float32, np.float64):
+            small = a.size == 0 or np.abs(a.astype(np.float64)).max() < (1 << 24)
+            a = a.astype(np.float32 if small else np.float64)
+        bad = ~np.isfinite(a)
+        if bad.any():
+            # every written value is finite: a colliding candidate's +inf cost (or any other
+            # non-finite entry) is written as 0, and <name>_nonfinite says where and what it was
+            # (0 finite, 1 +inf, -1 -inf, 2 NaN), so the pattern is compared like any output
+            code = np.where(np.isnan(a), 2, np.where(bad, np.sign(np.where(np.isnan(a), 0, a)), 0))
+            arrays[name + "_nonfinite"] = np.ascontiguousarray(code.astype(np.float32))
+            a = np.where(bad, 0, a).astype(a.dtype)
+        arrays[name] = np.ascontiguousarray(a)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        rng = np.random.default_rng(20240607)
+        keep = DUMP_LIMIT_BYTES / total
+        for name in sorted(arrays):
+            flat = arrays[name].reshape(-1)
+            idx = np.sort(rng.choice(flat.size, size=max(1, int(flat.size * keep)), replace=False))
+            arrays[name] = flat[idx]
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def rank_launch_cmd(argv, n, port):
     """The child command of `bench.py --gpus N` run without a launcher: this script under
     torch.distributed.run with N ranks on one node (same arguments)."""
@@ -820,7 +907,10 @@ def bench_line(args, ctx, meta, world, ns, native, B, elapsed, enqueue_s, kernel
     """The JSON line (rank 0).  `roofline` is the metric's HBM figure for the dominant kernel
     (algorithmic bytes per launch / HIP-event launch time; `traffic` and `traffic_frac` are the
     PMC-measured HBM bytes per launch and their rate against the peak); `binding_roofline` is
-    the resource that actually bounds it, FP64 VALU (PMC-executed flops per candidate)."""
+    the resource that actually bounds it, FP64 VALU (PMC-executed flops per candidate).  Both
+    rest on the roofline launches' time `kernel_s` (--full); without it (None) they are null."""
+    measured = kernel_s is not None
+    kernel_s = kernel_s if measured else float("nan")
     total = args.steps * B * world
     if ctx["kind"] == "multigoal":
         # every goal's mean set + samples, whatever the rank count; the forwarded best
@@ -882,7 +972,9 @@ def bench_line(args, ctx, meta, world, ns, native, B, elapsed, enqueue_s, kernel
                              exec_per * value / 1e12 / max(1, world)},
         "cpu_baseline": cpu,
     }
-    vi = extras.get("valu_issue")
+    if not measured:
+        line["roofline"] = line["binding_roofline"] = None
+    vi = extras.get("valu_issue") if measured else None
     if vi:
         # the FP32-filtered scan moved most of the arithmetic off FP64: the binding resource is
         # VALU issue (PMC: ~4 cycles per wave instruction per SIMD over the dispatch's cycles) at
@@ -967,6 +1059,14 @@ def main(argv=None):
                 full_step(counter[0])
                 counter[0] += 1
 
+        def outputs():
+            # the last step's lane: its per-candidate buffers and its (global) argmin record
+            if not counter[0]:
+                return {}
+            lane = (counter[0] - 1) % ns
+            return dict(ctx["lane_outputs"](lane), best=(gbest if world > 1 else local_best)[lane])
+        run_steps.outputs = outputs
+
     run_steps(args.warmup)
     torch.cuda.synchronize()
     if world > 1:
@@ -985,15 +1085,22 @@ def main(argv=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # roofline of the dominant kernel: HIP events on the stream the kernel runs on
-    stream = torch.cuda.current_stream()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(stream)
-    for i in range(args.roofline_launches):
-        kernel_only(i * B)
-    e1.record(stream)
-    torch.cuda.synchronize()
-    kernel_s = e0.elapsed_time(e1) / 1e3 / args.roofline_launches
+    if args.dump_outputs and (rank == 0 or ctx["kind"] == "multigoal"):
+        # the last timed step's results, before any later launch reuses its buffers (multigoal:
+        # every rank writes its own goals' files)
+        dump_outputs(args.dump_outputs, ctx["outputs"]() if "outputs" in ctx else run_steps.outputs())
+
+    kernel_s = None
+    if args.full:
+        # roofline of the dominant kernel: HIP events on the stream the kernel runs on
+        stream = torch.cuda.current_stream()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for i in range(args.roofline_launches):
+            kernel_only(i * B)
+        e1.record(stream)
+        torch.cuda.synchronize()
+        kernel_s = e0.elapsed_time(e1) / 1e3 / args.roofline_launches
 
     # the effective configuration of the timed launches, read before the CPU baseline's parity
     # batch (one launch of B candidates, which runs at the latency shape)
@@ -1002,7 +1109,7 @@ def main(argv=None):
     if "validate" in ctx:  # the timed launches lost no work (raises otherwise)
         meta.update(ctx["validate"]())
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, ctx, B, device)
 
     per_launch = ((ctx["samples"] + 2) * (len(ctx["mine"]) if args.mg_group else 1) if ctx["kind"] == "multigoal"
@@ -1025,11 +1132,11 @@ def main(argv=None):
     if lib_path:  # a variant build (profiling only): say so on the line
         meta["library"] = lib_path
     extras = {}
-    if rank == 0 and world == 1 and "isolated_step_us" in ctx:
+    if args.full and rank == 0 and world == 1 and "isolated_step_us" in ctx:
         # one plan()-sized batch alone on an idle stream (HIP events per launch): the latency
         # side of the same kernel, beside the fused multi-step throughput above
         extras["isolated_step_us"] = ctx["isolated_step_us"]()
-    if world == 1 and "set_order" in ctx and args.mode == "native":
+    if args.full and world == 1 and "set_order" in ctx and args.mode == "native":
         # what the hit-order pre-pass buys: the same timed run at scan order 1 (mean-path gap
         # pairs, bisection waypoints; bit-identical results), after the main region
         ctx["set_order"](1)

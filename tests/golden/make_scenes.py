@@ -7,8 +7,9 @@ data: every body (name, raw pos / orientation attributes, free joints) and every
 geom (contype or conaffinity non-zero) with its class defaults resolved into explicit raw
 attribute strings; visual meshes, materials, textures, lights, sites, inertials and actuator
 defaults are dropped.  Attribute strings are copied verbatim so both loaders see exactly the
-numbers the original file holds.  tests/test_scenes.py checks, where the reference is present,
-that the derived and original files give identical collidable geometry.
+numbers the original file holds.  tests/test_scenes_capi.py checks that the derived files and the
+original scene files (stored without their mesh assets under tests/golden/mjcf/) give identical
+collidable geometry.
 """
 import os
 import xml.etree.ElementTree as ET

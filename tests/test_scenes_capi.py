@@ -12,12 +12,15 @@ import pytest
 
 from oracle import mjcf_ref
 from oracle import oracle as O
-from tests.conftest import REFERENCE, ROOT, SCENES
+from tests.conftest import ROOT, SCENES
 
 import sspp_amd as S
 from sspp_amd import _lib
 
 SCENE_FILES = ["robocrane.xml", "stacking.xml", "planner.xml"]
+# the original scene files, stored as fixtures (their mesh assets are visual only and not needed:
+# neither loader opens them)
+ORIGINAL_DIR = os.path.join(ROOT, "tests", "golden")
 ORIGINALS = {"robocrane.xml": "mjcf/robocrane/robocrane.xml", "stacking.xml": "mjcf/stacking.xml",
              "planner.xml": "mjcf/planner.xml"}
 
@@ -80,12 +83,11 @@ def test_loader_matches_independent_reader(name):
         np.testing.assert_array_equal(np.asarray(v), np.asarray(r[k]).reshape(np.asarray(v).shape), err_msg=k)
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference checkout not present")
 @pytest.mark.parametrize("name", SCENE_FILES)
 def test_derived_scene_equals_original(name):
     """The committed collision-only scenes carry exactly the original collidable geometry."""
     d = mjcf_ref.load(os.path.join(SCENES, name))
-    o = mjcf_ref.load(os.path.join(REFERENCE, ORIGINALS[name]))
+    o = mjcf_ref.load(os.path.join(ORIGINAL_DIR, ORIGINALS[name]))
     for k in ("body_parent", "body_jnt_type", "body_qpos_adr", "body_pos", "body_quat", "qpos0",
               "exclude"):
         np.testing.assert_array_equal(d[k], o[k], err_msg=k)
@@ -94,7 +96,7 @@ def test_derived_scene_equals_original(name):
               "geom_pos", "geom_quat", "geom_margin"):
         np.testing.assert_array_equal(d[k], np.asarray(o[k])[keep], err_msg=k)
     # product loader on the original file gives the same arrays as the Python reader
-    a = S.Model(os.path.join(REFERENCE, ORIGINALS[name])).arrays()
+    a = S.Model(os.path.join(ORIGINAL_DIR, ORIGINALS[name])).arrays()
     for k, v in a.items():
         np.testing.assert_array_equal(np.asarray(v), np.asarray(o[k]).reshape(np.asarray(v).shape), err_msg=k)
 

@@ -1,5 +1,5 @@
-"""The roofline launches in a rocprofv3 kernel trace of bench.py: the average duration of the
-dominant kernel's last N dispatches of the most frequent grid (bench.py issues its
+"""The roofline launches in a rocprofv3 kernel trace of bench.py --full: the average duration of
+the dominant kernel's last N dispatches of the most frequent grid (bench.py --full issues its
 --roofline-launches (default 20) after the timed loop, back to back on one stream), against the
 average over every dispatch (the timed loop's launches overlap on several streams, so each one
 takes longer than it does alone).
