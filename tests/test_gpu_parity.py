@@ -5,6 +5,10 @@ follow the oracle's operation order, so the tests hold them to 1e-12 (SamplingPa
 and 1e-9 (TaskSpacePlanner: control points from the same Householder QR replay as the oracle;
 costs summed in the canonical lane order); feasibility flags and the selected index
 bit-identical.
+
+The scenes here are the three shipped ones; tests/test_gpu_synthetic_scenes.py holds the same
+bars on authored scenes where these never go (spheres, tilted planes, more than 64 pairs, statics
+outside the FP32 filter's range, two movers).
 """
 import os
 
