@@ -74,6 +74,7 @@ def lib():
                                      C.c_int64, C.c_int64, _d, C.c_int]
         L.or_sample_tsp.argtypes = [_d, _d, C.c_int, _d, _d, C.c_double, C.c_uint64, C.c_int64,
                                     C.c_int64, _d]
+        L.or_sample_tsp_tries.argtypes = L.or_sample_tsp.argtypes + [_i32]
         L.or_point_contacts.argtypes = [C.c_void_p, _d, C.c_int, C.POINTER(C.c_double),
                                         C.POINTER(C.c_int)]
         L.or_fk_geoms.argtypes = [C.c_void_p, _d, _d, _d]
@@ -194,10 +195,17 @@ def sample_sspp(init_ctrl, p, sigma, limits, seed, first, B, sampler=SAMPLER_FP6
     return out
 
 
-def sample_tsp(mean, sigma, lo, hi, z_min, seed, first, B):
+def sample_tsp(mean, sigma, lo, hi, z_min, seed, first, B, with_tries=False):
+    """Sampler::sample_set for candidate ids [first, first + B).  with_tries: also the (B, K, 3)
+    array of the accepted normal draw (1..99) of x, y, z, 0 where the uniform fallback ran."""
     mean, sigma = _f64(mean).reshape(-1, 4), _f64(sigma).reshape(-1, 4)
     K = mean.shape[0]
     out = np.zeros((B, K, 4))
+    if with_tries:
+        tries = np.zeros((B, K, 3), np.int32)
+        lib().or_sample_tsp_tries(mean, sigma, K, _f64(lo).reshape(4), _f64(hi).reshape(4),
+                                  float(z_min), seed, first, B, out, tries)
+        return out, tries
     lib().or_sample_tsp(mean, sigma, K, _f64(lo).reshape(4), _f64(hi).reshape(4),
                         float(z_min), seed, first, B, out)
     return out

@@ -462,9 +462,11 @@ void or_sample_sspp(const double* init_ctrl, int n, int D, int p, double sigma,
     }
 }
 
-void or_sample_tsp(const double* mean, const double* sigma, int K, const double* lo,
-                   const double* hi, double z_min, uint64_t seed, int64_t first, int64_t B,
-                   double* vias_out) {
+/* tries (optional) [B][K][3]: the normal draw (1..99) that fell inside the bounds, 0 when all
+   99 missed and the value is the uniform fallback */
+void or_sample_tsp_tries(const double* mean, const double* sigma, int K, const double* lo,
+                         const double* hi, double z_min, uint64_t seed, int64_t first, int64_t B,
+                         double* vias_out, int32_t* tries) {
     /* include/sspp/tsp_sampler.h:12-51 */
     for (int64_t b = 0; b < B; ++b) {
         uint64_t g = (uint64_t)(first + b);
@@ -480,13 +482,14 @@ void or_sample_tsp(const double* mean, const double* sigma, int K, const double*
                     or_normal_pair(seed, g, (uint32_t)(((v * 4 + i) << 7) | t), 1u, &z0, &z1);
                     val = z0 * s[i];
                     val = val + m[i];
-                    if (!(val < lo[i] || val > hi[i])) { ok = 1; break; }
+                    if (!(val < lo[i] || val > hi[i])) { ok = t + 1; break; }
                 }
                 if (!ok) {
                     double u = uniform01(seed, g, (uint32_t)(((v * 4 + i) << 7) | 127), 1u);
                     val = u * (hi[i] - lo[i]);
                     val = val + lo[i];
                 }
+                if (tries) tries[((size_t)b * K + v) * 3 + i] = ok;
                 pt[i] = val;
             }
             if (lo[3] != hi[3]) {
@@ -504,6 +507,12 @@ void or_sample_tsp(const double* mean, const double* sigma, int K, const double*
             if (pt[2] < z_min) pt[2] = z_min;
         }
     }
+}
+
+void or_sample_tsp(const double* mean, const double* sigma, int K, const double* lo,
+                   const double* hi, double z_min, uint64_t seed, int64_t first, int64_t B,
+                   double* vias_out) {
+    or_sample_tsp_tries(mean, sigma, K, lo, hi, z_min, seed, first, B, vias_out, NULL);
 }
 
 /* ------------------------------------------------------------------ scene */

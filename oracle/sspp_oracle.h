@@ -101,6 +101,11 @@ void   or_sample_sspp(const double* init_ctrl, int n, int D, int p, double sigma
 void   or_sample_tsp(const double* mean /* [K][4] */, const double* sigma /* [K][4] */, int K,
                      const double* lo, const double* hi, double z_min, uint64_t seed,
                      int64_t first, int64_t B, double* vias_out);
+/* the same draws; tries [B][K][3] (optional): the accepted normal draw 1..99 of x, y, z, or 0
+   when all 99 fell outside the bounds and the value is the uniform fallback */
+void   or_sample_tsp_tries(const double* mean, const double* sigma, int K, const double* lo,
+                           const double* hi, double z_min, uint64_t seed, int64_t first, int64_t B,
+                           double* vias_out, int32_t* tries);
 
 /* ---- collision / FK ---- */
 /* q: dof values (mode 0) or (x,y,z,yaw) (mode 1).  Returns contact count (all pairs
