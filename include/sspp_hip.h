@@ -65,7 +65,10 @@ extern "C" {
 #define SSPP_E_IO (-6)
 #define SSPP_E_INCOMPLETE (-7) /* a result record reports lost work (sspp_best::reserved != 0) */
 
-/* MuJoCo mjtGeom codes for the supported primitives */
+/* MuJoCo mjtGeom codes for the supported primitives.  Collision pairs: every pair of plane,
+   sphere, capsule, cylinder and box except cylinder-cylinder and capsule-cylinder (a scene that
+   needs one is refused with SSPP_E_UNSUPPORTED); meshes are parsed but never collide.  A capsule
+   is size[0] = radius, size[1] = half-length of its cylindrical part, along the frame's z axis. */
 #define SSPP_GEOM_PLANE 0
 #define SSPP_GEOM_SPHERE 2
 #define SSPP_GEOM_CAPSULE 3
@@ -260,6 +263,8 @@ void sspp_job_free(sspp_job* job);
                                    instead of finishing them, so the lost-work check must fire  */
 #define SSPP_OPT_SPLIT_HANDOFFS 22 /* get (synchronous): slots handed to last workgroups so far */
 #define SSPP_OPT_SPLIT_LOST 23  /* get (synchronous): survivors lost so far (0 unless DROP)     */
+#define SSPP_OPT_CAPSULE 24     /* get: the sampled-candidate table has capsule pairs (the kernels
+                                   that carry the capsule colliders run; mirrors SSPP_OPT_CYLBOX)  */
 #define SSPP_OPT_TSP_REP 19     /* TaskSpacePlanner k_tsp form 3: sub-batches of candidates
                                    per workgroup (one prologue for all of them), 1..16, -1 by batch
                                    size; get: the last k_tsp launch's                            */

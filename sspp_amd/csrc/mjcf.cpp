@@ -165,8 +165,33 @@ struct Loader {
         auto ps = floats(a.count("pos") ? a["pos"] : "0 0 0");
         if (ps.size() != 3) throw std::runtime_error("geom pos needs 3 numbers");
         for (int k = 0; k < 3; ++k) g.pos[k] = ps[k];
-        orientation(a, comp, g.quat);
-        g.ct = a.count("contype") ? std::stoi(a["contype"]) : 1;
+        if (a.count("fromto") && (g.type == 3 || g.type == 5)) {
+            // capsule / cylinder given by its segment: pos = the midpoint, size[1] = half its
+            // length (size supplies the radius only), quat = the shortest rotation taking +z to
+            // d = (to - from) / |to - from|, i.e. (1 + d_z, -d_y, d_x, 0) normalised.  (MuJoCo
+            // aligns the frame's z axis with from - to instead; the solid is the same.)  For
+            // d_z < 0, 1 + d_z is formed as (d_x^2 + d_y^2) / (1 - d_z), free of cancellation;
+            // exactly antiparallel (d = -z) is the rotation by pi about x.
+            auto ft = floats(a["fromto"]);
+            if (ft.size() != 6) throw std::runtime_error("fromto needs 6 numbers");
+            const double v[3] = {ft[3] - ft[0], ft[4] - ft[1], ft[5] - ft[2]};
+            const double len = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+            if (!(len > 0.0)) throw std::runtime_error("geom '" + g.name + "': zero-length fromto");
+            const double d[3] = {v[0] / len, v[1] / len, v[2] / len};
+            for (int k = 0; k < 3; ++k) g.pos[k] = 0.5 * (ft[k] + ft[3 + k]);
+            g.size[1] = 0.5 * len;
+            g.size[2] = 0.0;
+            const double s2 = d[0] * d[0] + d[1] * d[1];
+            g.quat[0] = d[2] >= 0.0 ? 1.0 + d[2] : s2 / (1.0 - d[2]);
+            g.quat[1] = -d[1]; g.quat[2] = d[0]; g.quat[3] = 0.0;
+            if (d[2] < 0.0 && s2 == 0.0) { g.quat[0] = 0.0; g.quat[1] = 1.0; g.quat[2] = 0.0; }
+            normq(g.quat);
+        } else {
+            orientation(a, comp, g.quat);
+        }
+        if (g.type == 3 && !(g.size[0] > 0.0 && g.size[1] > 0.0))
+            throw std::runtime_error("capsule geom '" + g.name + "' needs a positive radius and half-length");
+        g.ct =a.count("contype") ? std::stoi(a["contype"]) : 1;
         g.ca = a.count("conaffinity") ? std::stoi(a["conaffinity"]) : 1;
         g.margin = a.count("margin") ? std::stod(a["margin"]) : 0.0;
         g.body = body;

@@ -1096,13 +1096,173 @@ SSPP_HD bool cyl_box_overlap(const double* pa, const double* ma, const double* s
                           b.R, b.H, thr);
 }
 
+// ---------------------------------------------------------------- capsules
+// A capsule is the segment c +- h a (a = the frame's z column, h = size[1]) with radius r =
+// size[0]; every capsule test reduces to sphere tests at points of the segment, so the contact
+// rule is the sphere colliders' (contact iff dist <= margin, deep iff dist < -1e-3).  DESIGN.md §4.
+SSPP_HD double clamp_pm(double x, double h) { return x > h ? h : (x < -h ? -h : x); }
+// The colliders' optional last argument `dout` receives the signed distance of every sphere
+// test run, in the rule's order (host checks only; the kernels pass none and the stores vanish).
+// one signed distance accumulated into a (contacts, deep) pair
+SSPP_HD void cap_tally(double dist, double margin, int* nc, int* nd, double* dout) {
+    const int c = dist <= margin;
+    *nc += c;
+    *nd += (c && dist < deep_thr()) ? 1 : 0;
+    if (dout) *dout = dist;
+}
+// one sphere-sphere test (col_sphere_sphere's distance) accumulated likewise
+SSPP_HD void cap_sphere_test(const double* p1, double r1, const double* p2, double r2, double margin,
+                             int* nc, int* nd, double* dout) {
+    const double d[3] = {p2[0] - p1[0], p2[1] - p1[1], p2[2] - p1[2]};
+    cap_tally(sqrt(dot3(d, d)) - (r1 + r2), margin, nc, nd, dout);
+}
+// plane-capsule: one sphere-plane test per segment end, +h then -h (0-2 contacts)
+SSPP_HD int col_plane_capsule(const double* pp, const double* pm, const double* cp, const double* cm,
+                              const double* sz, double margin, int* nd, double* dout = nullptr) {
+    double a[3], n[3];
+    col3(cm, 2, a);
+    col3(pm, 2, n);
+    int nc = 0, ndd = 0;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const double h = s ? -sz[1] : sz[1];
+        // col_plane_sphere's distance at the end c + h a
+        const double d[3] = {fma(h, a[0], cp[0]) - pp[0], fma(h, a[1], cp[1]) - pp[1], fma(h, a[2], cp[2]) - pp[2]};
+        cap_tally(dot3(d, n) - sz[0], margin, &nc, &ndd, dout ? dout + s : nullptr);
+    }
+    *nd = ndd;
+    return nc;
+}
+// sphere-capsule: the sphere against a sphere of radius r at the segment's point nearest its centre
+SSPP_HD int col_sphere_capsule(const double* sp, double rs, const double* cp, const double* cm,
+                               const double* sz, double margin, int* nd, double* dout = nullptr) {
+    double a[3];
+    col3(cm, 2, a);
+    const double d[3] = {sp[0] - cp[0], sp[1] - cp[1], sp[2] - cp[2]};
+    const double x = clamp_pm(dot3(a, d), sz[1]);
+    const double q[3] = {fma(x, a[0], cp[0]), fma(x, a[1], cp[1]), fma(x, a[2], cp[2])};
+    int nc = 0;
+    *nd = 0;
+    cap_sphere_test(sp, rs, q, sz[0], margin, &nc, nd, dout);
+    return nc;
+}
+// capsule-capsule.  General position: the segments' closest pair (x1, x2) — x1 from the 2x2
+// system, clamped; x2 = the point of line 2 nearest that point of segment 1 (for an unclamped x1
+// this IS the system's x2, formed from x1 so that a badly conditioned near-parallel system costs
+// no accuracy: the distance is flat along the common direction); x2 clamped and x1 recomputed,
+// clamped — then one sphere-sphere test (0-1 contacts).  Parallel axes (|det| < 1e-15): each
+// capsule's two ends against their nearest points of the other segment, +h1, -h1, +h2, -h2,
+// until two contacts are found (0-2 contacts).
+SSPP_HD int col_capsule_capsule(const double* p1, const double* m1, const double* s1, const double* p2,
+                                const double* m2, const double* s2, double margin, int* nd,
+                                double* dout = nullptr) {
+    double a1[3], a2[3];
+    col3(m1, 2, a1);
+    col3(m2, 2, a2);
+    const double h1 = s1[1], h2 = s2[1];
+    const double dif[3] = {p1[0] - p2[0], p1[1] - p2[1], p1[2] - p2[2]};
+    const double ma = dot3(a1, a1), mb = -dot3(a1, a2), mc = dot3(a2, a2);
+    const double u = -dot3(a1, dif), v = dot3(a2, dif);
+    const double det = ma * mc - mb * mb;
+    int nc = 0, ndd = 0;
+    if (fabs(det) < kMinVal) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            if (nc < 2) {
+                const bool first = t < 2;  // an end of capsule 1 (else of capsule 2)
+                const double h = first ? ((t & 1) ? -h1 : h1) : ((t & 1) ? -h2 : h2);
+                double e[3], q[3];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) e[i] = first ? fma(h, a1[i], p1[i]) : fma(h, a2[i], p2[i]);
+                // the other segment's point nearest e
+                const double w[3] = {e[0] - (first ? p2[0] : p1[0]), e[1] - (first ? p2[1] : p1[1]),
+                                     e[2] - (first ? p2[2] : p1[2])};
+                const double x = first ? clamp_pm(dot3(a2, w), h2) : clamp_pm(dot3(a1, w), h1);
+#pragma unroll
+                for (int i = 0; i < 3; ++i) q[i] = first ? fma(x, a2[i], p2[i]) : fma(x, a1[i], p1[i]);
+                if (first) cap_sphere_test(e, s1[0], q, s2[0], margin, &nc, &ndd, dout ? dout + t : nullptr);
+                else cap_sphere_test(q, s1[0], e, s2[0], margin, &nc, &ndd, dout ? dout + t : nullptr);
+            }
+        }
+        *nd = ndd;
+        return nc;
+    }
+    double x1 = clamp_pm((mc * u - mb * v) / det, h1);
+    double x2 = (v - mb * x1) / mc;
+    if (x2 > h2) { x2 = h2; x1 = clamp_pm((u - mb * h2) / ma, h1); }
+    else if (x2 < -h2) { x2 = -h2; x1 = clamp_pm((u + mb * h2) / ma, h1); }
+    const double q1[3] = {fma(x1, a1[0], p1[0]), fma(x1, a1[1], p1[1]), fma(x1, a1[2], p1[2])};
+    const double q2[3] = {fma(x2, a2[0], p2[0]), fma(x2, a2[1], p2[1]), fma(x2, a2[2], p2[2])};
+    cap_sphere_test(q1, s1[0], q2, s2[0], margin, &nc, &ndd, dout);
+    *nd = ndd;
+    return nc;
+}
+// F'(t) = sum_k w_k d_k of F(t) = 1/2 |w(t)|^2, w_k = p_k - clamp(p_k, -e_k, e_k), p = P + t d
+// (box frame): non-decreasing and piecewise linear in t
+SSPP_HD double capbox_dF(const double* P, const double* d, const double* e, double t) {
+    double g = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double p = fma(t, d[k], P[k]);
+        g = fma(p - clamp_pm(p, e[k]), d[k], g);
+    }
+    return g;
+}
+// capsule-box: dist = d_seg - r, d_seg the Euclidean distance of the segment to the solid box
+// (0 when they meet: the depth of a segment inside the box is not measured).  d_seg is the
+// minimum of the convex F over [-h, h]: F' at the two ends and at its (at most 6) breakpoints
+// p_k = +-e_k clipped to [-h, h] gives the tightest bracket of its sign change, inside which F'
+// is linear, so one interpolation is exact.  Fixed trip counts, no indexed local arrays.
+SSPP_HD int col_capsule_box(const double* cp, const double* cm, const double* sz, const double* bp,
+                            const double* bm, const double* e, double margin, int* nd,
+                            double* dout = nullptr) {
+    double a[3], ax[3], P[3], d[3];
+    col3(cm, 2, a);
+    const double T[3] = {cp[0] - bp[0], cp[1] - bp[1], cp[2] - bp[2]};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { col3(bm, k, ax); P[k] = dot3(ax, T); d[k] = dot3(ax, a); }
+    const double h = sz[1];
+    double lo = -h, hi = h;
+    double glo = capbox_dF(P, d, e, lo), ghi = capbox_dF(P, d, e, hi);
+    double t;
+    if (glo >= 0.0) t = lo;
+    else if (ghi <= 0.0) t = hi;
+    else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const double f = s ? e[k] : -e[k];
+                const double tb = d[k] != 0.0 ? clamp_pm((f - P[k]) / d[k], h) : -h;
+                const double g = capbox_dF(P, d, e, tb);
+                if (g <= 0.0 && tb > lo) { lo = tb; glo = g; }
+                if (g >= 0.0 && tb < hi) { hi = tb; ghi = g; }
+            }
+        }
+        t = ghi > glo ? fma(hi - lo, -glo / (ghi - glo), lo) : lo;
+    }
+    double w2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double p = fma(t, d[k], P[k]);
+        const double w = p - clamp_pm(p, e[k]);
+        w2 = fma(w, w, w2);
+    }
+    int nc = 0;
+    *nd = 0;
+    cap_tally(sqrt(w2) - sz[0], margin, &nc, nd, dout);
+    return nc;
+}
+
 // Supported narrowphase pair? (types ordered t1 <= t2)
 SSPP_HD bool pair_supported(int t1, int t2) {
     if (t1 > t2) { int t = t1; t1 = t2; t2 = t; }
-    if (t1 == 0) return t2 == 0 || t2 == 2 || t2 == 5 || t2 == 6;
-    if (t1 == 2) return t2 == 2 || t2 == 5 || t2 == 6;
+    if (t1 == 0) return t2 == 0 || t2 == 2 || t2 == 3 || t2 == 5 || t2 == 6;
+    if (t1 == 2) return t2 == 2 || t2 == 3 || t2 == 5 || t2 == 6;
+    if (t1 == 3) return t2 == 3 || t2 == 6;  // capsule-cylinder: not built
     return (t1 == 5 && t2 == 6) || (t1 == 6 && t2 == 6);
 }
+SSPP_HD bool pair_has_capsule(int t1, int t2) { return t1 == 3 || t2 == 3; }
 
 // Narrowphase dispatch.  Geom 1 must be the first by (type, model index), like the oracle.
 // NEED_DEEP=false: returns the contact count (SamplingPathPlanner feasibility needs > 0).
@@ -1116,20 +1276,34 @@ SSPP_HD bool pair_supported(int t1, int t2) {
 // CB: 0 no cylinder-box pairs (code compiled out), 1 the exact test (vertical-cylinder /
 // upright-box pairs take cb_upright_sd), 2 every cylinder-box pair is vertical / upright
 // (host-checked): cb_upright_sd only, the candidate search compiled out.
-template <bool NEED_DEEP, int CB = 1, bool OUTLINE = false, bool DEFER = false, bool UP = false>
+// CAP = false compiles out the capsule colliders (only for pair tables without a capsule pair:
+// the kernels select it from the table, sspk::kscene); the host always carries them.
+// CAPDEFER (feasibility only): a pair with a capsule in it returns -1, undecided, like a
+// deferred cylinder-box pair, and the caller settles it later (k_sspp_c2f's pair loops carry no
+// capsule code; c2f_cb_exact does).
+template <bool NEED_DEEP, int CB = 1, bool OUTLINE = false, bool DEFER = false, bool UP = false, bool CAP = true,
+          bool CAPDEFER = false>
 SSPP_HD int collide(int t1, const double* p1, const double* m1, const double* s1, int t2,
                     const double* p2, const double* m2, const double* s2, double margin, int* nd) {
     *nd = 0;
+    if (CAP && CAPDEFER && !NEED_DEEP && pair_has_capsule(t1, t2)) return -1;
     if (t1 == 0) {
         if (t2 == 6) return col_plane_box(p1, m1, p2, m2, s2, margin, nd);
         if (t2 == 2) return col_plane_sphere(p1, m1, p2, s2[0], margin, nd);
         if (t2 == 5) return col_plane_cyl(p1, m1, p2, m2, s2, margin, nd);
+        if (CAP && t2 == 3) return col_plane_capsule(p1, m1, p2, m2, s2, margin, nd);
         return 0;
     }
     if (t1 == 2) {
         if (t2 == 2) return col_sphere_sphere(p1, s1[0], p2, s2[0], margin, nd);
         if (t2 == 6) return col_sphere_box(p1, s1[0], p2, m2, s2, margin, nd);
         if (t2 == 5) return col_sphere_cyl(p1, s1[0], p2, m2, s2, margin, nd);
+        if (CAP && t2 == 3) return col_sphere_capsule(p1, s1[0], p2, m2, s2, margin, nd);
+        return 0;
+    }
+    if (CAP && t1 == 3) {
+        if (t2 == 3) return col_capsule_capsule(p1, m1, s1, p2, m2, s2, margin, nd);
+        if (t2 == 6) return col_capsule_box(p1, m1, s1, p2, m2, s2, margin, nd);
         return 0;
     }
     if (t1 == 5) {  // cylinder-box: exact signed distance test, one contact (MuJoCo's convex collider)

@@ -70,12 +70,20 @@ constexpr int kBlock = 256;
 constexpr int kMaxMovers = 2;
 constexpr int kMaxSteps = 64;  // steps per launch (k_sspp_c2f)
 
+// what a pair contributes to its table's kernel selection (KScene::cylbox, sspp_job::cb_*)
+constexpr int kTableCylBox = 1, kTableCapsule = 2;
+__host__ __device__ inline int table_bits(int tg, int to) {
+    return (((tg == 5 && to == 6) || (tg == 6 && to == 5)) ? kTableCylBox : 0) |
+           (sspd::pair_has_capsule(tg, to) ? kTableCapsule : 0);
+}
+
 struct KScene {
     int npairs;
     int onegeom;        // every pair shares one moving geom: its pose is computed once
     int static_block;   // sspp: env-env contacts counted and present -> nothing feasible
     double static_cost; // tsp: Collision.h cost of env-env contacts, added per waypoint
-    int cylbox;         // some moving pair is cylinder-box (selects the kernels that carry that code)
+    int cylbox;         // table_bits of the moving pairs: non-zero selects the kernels that carry the
+                        // cylinder-box and capsule code (CBX / CB = 1)
     int upright;        // tsp: every box-box pair is upright for a yaw-only mover (k_tsp<..., UP>)
     int cbup;           // tsp: every cylinder-box pair is vertical / upright (collide<..., CB = 2>)
 };
@@ -702,9 +710,9 @@ __device__ int point_collide(const double* q, const KScene& sc, const SceneT& T,
                                            : box_box_deep_class(op, om, pr.osize, gp, gmat, G.size));
                 nd = c < 0 ? 0 : (c == 6 ? 1 : kBbPend + c);
             } else if (gfirst) {
-                nc = collide<DEEP, CB, DEEP, false, UP>(G.type, gp, gmat, G.size, pr.otype, op, om, pr.osize, pr.margin, &nd);
+                nc = collide<DEEP, CB, DEEP, false, UP, CB == 1>(G.type, gp, gmat, G.size, pr.otype, op, om, pr.osize, pr.margin, &nd);
             } else {
-                nc = collide<DEEP, CB, DEEP, false, UP>(pr.otype, op, om, pr.osize, G.type, gp, gmat, G.size, pr.margin, &nd);
+                nc = collide<DEEP, CB, DEEP, false, UP, CB == 1>(pr.otype, op, om, pr.osize, G.type, gp, gmat, G.size, pr.margin, &nd);
             }
         }
         if (DEEP) TSP_STAT(5, nd > 0);
@@ -927,8 +935,9 @@ __device__ __forceinline__ void finish_batch(const BlockBest bb, BlockBest* __re
 //   phase 2  the survivors (few: the feasible ones plus the rare misses) are compacted in LDS
 //            and their remaining waypoints spread over all NT lanes in rounds; a contact clears
 //            the candidate's LDS flag and the next round drops the candidate;
-//   settle   cylinder-box pairs the scans left undecided (collide<..., DEFER>) get the exact
-//            test, out of line, for the (rare) candidates that have no other contact;
+//   settle   cylinder-box and capsule pairs the scans left undecided (collide<..., DEFER,
+//            CAPDEFER>) get the exact test, out of line, for the candidates that have no other
+//            contact (rare for cylinder-box pairs; every candidate that passes near a capsule);
 //   phase 3  arc length of the collision-free candidates, in the canonical reduction order of
 //            oracle/sspp_oracle.c::or_canon_sum;
 //   phase 4  block argmin + the fused batch argmin (finish_batch).
@@ -1155,7 +1164,11 @@ __device__ __forceinline__ void eval_split_g(const double* sm, int mine, int fix
 // 1143-1152 M cand/s on the 20-step run), and the next round drops the decided survivors anyway.
 // A cylinder-box pair that passes the bounding-sphere test sets dfr (undecided) and counts as
 // no contact here (collide<..., DEFER>); the settle step decides it with the exact test.
-template <int D, int NM, bool ONEGEOM>
+// CAP: 0 no capsule pairs in the table (their colliders compiled out), 1 a capsule pair past the
+// bounding-sphere test is left undecided like a cylinder-box pair (k_sspp_c2f: settled by
+// c2f_cb_exact, so the pair loops of the cylinder-box kernels are what they were), 2 tested here
+// (k_sspp_census).
+template <int D, int NM, bool ONEGEOM, int CAP = 0>
 __device__ __forceinline__ bool scan_pairs(const double* q, bool live, unsigned long long mymask,
                                            unsigned long long umask, unsigned long long gbits,
                                            int* flag, const KScene& sc, const SceneT& T, bool& dfr) {
@@ -1214,8 +1227,8 @@ __device__ __forceinline__ bool scan_pairs(const double* q, bool live, unsigned 
                 }
                 int nd = 0;
                 const bool gfirst = (G.type < pr.otype) || (G.type == pr.otype && G.orig < pr.oorig);
-                if (gfirst) nc = collide<false, true, false, true>(G.type, gp, gmat, G.size, pr.otype, op, om, pr.osize, pr.margin, &nd);
-                else nc = collide<false, true, false, true>(pr.otype, op, om, pr.osize, G.type, gp, gmat, G.size, pr.margin, &nd);
+                if (gfirst) nc = collide<false, true, false, true, false, CAP != 0, CAP == 1>(G.type, gp, gmat, G.size, pr.otype, op, om, pr.osize, pr.margin, &nd);
+                else nc = collide<false, true, false, true, false, CAP != 0, CAP == 1>(pr.otype, op, om, pr.osize, G.type, gp, gmat, G.size, pr.margin, &nd);
                 if (nc < 0) { dfr = true; nc = 0; }
             }
         }
@@ -1402,7 +1415,7 @@ __device__ __forceinline__ unsigned long long wave_or64(unsigned long long m) {
 // cylinder-box pair left undecided counts as no contact: the census only steers the order).
 // Output: hit bits [M][ceil((W+1) / 64)], bit i = contact at waypoint i.
 constexpr int kCensusThreads = 256;
-template <int D, int NM, int P, bool ONEGEOM>
+template <int D, int NM, int P, bool ONEGEOM, bool CAP = false>
 __global__ __launch_bounds__(kCensusThreads) void k_sspp_census(
     KScene sc, SceneT T, int n, int W, int sampler, double sigma, unsigned long long seed,
     const double* __restrict__ tab, const int* __restrict__ span, const double* __restrict__ init_ctrl,
@@ -1427,7 +1440,7 @@ __global__ __launch_bounds__(kCensusThreads) void k_sspp_census(
         double q[D];
         eval_split_g<D, P>(smem, ndof, 0, r0, r1, tab + (live ? j : 0) * P1, span[live ? j : 0], q);
         bool dfr = false;
-        const bool h = scan_pairs<D, NM, ONEGEOM>(q, live, ~0ull, ~0ull, 1ull << (tid & 63), nullptr, sc, T, dfr);
+        const bool h = scan_pairs<D, NM, ONEGEOM, CAP ? 2 : 0>(q, live, ~0ull, ~0ull, 1ull << (tid & 63), nullptr, sc, T, dfr);
         if (h && live) atomicOr(hits + (long long)m * nw + (j >> 6), 1ull << (j & 63));
     }
 }
@@ -1435,8 +1448,9 @@ __global__ __launch_bounds__(kCensusThreads) void k_sspp_census(
 #ifndef SSPP_CB_INLINE
 #define SSPP_CB_INLINE __attribute__((noinline))
 #endif
-// The exact cylinder-box test (witnesses + candidate search, sspd::cyl_box_overlap) of one
-// waypoint of one candidate over its cylinder-box pairs.  Out of line: it runs only for the
+// The exact cylinder-box test (witnesses + candidate search, sspd::cyl_box_overlap) and the
+// capsule colliders of one waypoint of one candidate over its cylinder-box and capsule pairs
+// (the pairs the scans leave undecided).  Out of line: it runs only for the
 // candidates the scans left undecided, and its registers stay out of the kernel's pair loops.
 template <int D, int NM, int P>
 __device__ SSPP_CB_INLINE bool c2f_cb_exact(const double* sm, int mine, int fix, int r0, int r1,
@@ -1452,7 +1466,7 @@ __device__ SSPP_CB_INLINE bool c2f_cb_exact(const double* sm, int mine, int fix,
         if (k < 64 && !((mask >> k) & 1ull)) continue;
         const DPair pr = load_pair(pairs + k);
         const DGeom G = load_geom(geoms + pr.gm);
-        if (!((G.type == 5 && pr.otype == 6) || (G.type == 6 && pr.otype == 5))) continue;
+        if (table_bits(G.type, pr.otype) == 0) continue;  // cylinder-box and capsule pairs only
         const bool second = NM > 1 && G.mover == 1;
         double gp[3], gmat[9], op_[3], om_[9];
         geom_pose(second ? mp[NM - 1] : mp[0], second ? mR[NM - 1] : mR[0], G, gp, gmat);
@@ -1471,8 +1485,8 @@ __device__ SSPP_CB_INLINE bool c2f_cb_exact(const double* sm, int mine, int fix,
         if (!pair_near(pr, G.rbound, gp, op, om)) continue;
         int nd = 0;
         const bool gfirst = (G.type < pr.otype) || (G.type == pr.otype && G.orig < pr.oorig);
-        const int nc = gfirst ? collide<false>(G.type, gp, gmat, G.size, pr.otype, op, om, pr.osize, pr.margin, &nd)
-                              : collide<false>(pr.otype, op, om, pr.osize, G.type, gp, gmat, G.size, pr.margin, &nd);
+        const int nc = gfirst ? collide<false, 1, false, false, false, true>(G.type, gp, gmat, G.size, pr.otype, op, om, pr.osize, pr.margin, &nd)
+                              : collide<false, 1, false, false, false, true>(pr.otype, op, om, pr.osize, G.type, gp, gmat, G.size, pr.margin, &nd);
         if (nc > 0) return true;
     }
     return false;
@@ -1636,7 +1650,7 @@ __device__ __forceinline__ void surv_finish(const SsppC2F& a, const SceneT& TT, 
 #ifndef SSPP_ABLATE
 #define SSPP_ABLATE 0
 #endif
-// CBX: the pair table has cylinder-box pairs, so the kernel carries the settle step (its
+// CBX: the pair table has cylinder-box or capsule pairs, so the kernel carries the settle step (its
 // out-of-line exact test costs the whole kernel registers: 96 -> 128 VGPRs and scratch)
 // SPLIT: the split launch's instance (single-geom movers without cylinder-box pairs): phase 1,
 // then the survivor queue; the in-workgroup phases 2-4 are unreachable there and compiled out, so
@@ -1794,13 +1808,13 @@ __global__ __launch_bounds__(NT, (NT <= SSPP_C2F_FIVE_MAX && ONEGEOM) ? SSPP_C2F
                 if (__ballot(need) != 0ull) {
                     double q[D];
                     eval_split_g<D, P>(smem, own, o_fix, r0, r1, otab + row_p1 * P1, span_p1, q);
-                    ghit = scan_pairs<D, NM, ONEGEOM>(q, need, amb, wave_or64(need ? amb : 0ull), gbits, nullptr,
+                    ghit = scan_pairs<D, NM, ONEGEOM, CBX ? 1 : 0>(q, need, amb, wave_or64(need ? amb : 0ull), gbits, nullptr,
                                                       a.sc, TT, dfr) || ghit;
                 }
             } else {
                 double q[D];
                 eval_split_g<D, P>(smem, own, o_fix, r0, r1, otab + row_p1 * P1, span_p1, q);
-                ghit = scan_pairs<D, NM, ONEGEOM>(q, live, ~0ull, ~0ull, gbits, nullptr, a.sc, TT, dfr);
+                ghit = scan_pairs<D, NM, ONEGEOM, CBX ? 1 : 0>(q, live, ~0ull, ~0ull, gbits, nullptr, a.sc, TT, dfr);
             }
         }
         const bool gdef = (__ballot(dfr) & gbits) != 0ull;
@@ -2259,13 +2273,13 @@ __global__ __launch_bounds__(NT, (NT <= SSPP_C2F_FIVE_MAX && ONEGEOM) ? SSPP_C2F
                         if (__ballot(need) != 0ull) {
                             double q[D];
                             eval_split_g<D, P>(smem, o_own + s * nrd, o_fix, r0, r1, otab + j * P1, ospan[j], q);
-                            h = scan_pairs<D, NM, ONEGEOM>(q, need, amb, wave_or64(need ? amb : 0ull), gb, s_feas + s,
+                            h = scan_pairs<D, NM, ONEGEOM, CBX ? 1 : 0>(q, need, amb, wave_or64(need ? amb : 0ull), gb, s_feas + s,
                                                            a.sc, TT, dfr) || h;
                         }
                     } else {
                         double q[D];
                         eval_split_g<D, P>(smem, o_own + s * nrd, o_fix, r0, r1, otab + j * P1, ospan[j], q);
-                        h = scan_pairs<D, NM, ONEGEOM>(q, live, mym, umask & gmask, gb, s_feas + s, a.sc, TT, dfr);
+                        h = scan_pairs<D, NM, ONEGEOM, CBX ? 1 : 0>(q, live, mym, umask & gmask, gb, s_feas + s, a.sc, TT, dfr);
                     }
                     if (h) __hip_atomic_store(s_feas + s, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     if (dfr) __hip_atomic_store(s_defer + s, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -3172,7 +3186,9 @@ inline KScene kscene(const sspp_scene* s, bool tsp, bool generic = false) {
     for (const DPair& p : s->pairs) {
         const DGeom& g = s->geoms[p.gm];
         const int tg = g.type;
-        k.cylbox |= (tg == 5 && p.otype == 6) || (tg == 6 && p.otype == 5);
+        k.cylbox |= table_bits(tg, p.otype);
+        // capsule pairs ride in the generic instantiations (CB = 1, no upright shortcuts)
+        if (sspd::pair_has_capsule(tg, p.otype)) k.upright = k.cbup = 0;
         // the mover's yaw rotation keeps m[2] = m[5] = m[6] = m[7] = 0 exactly (mover_poses
         // MODE 1, geom_rot_t, matmul3 for a moving partner) when the relative rotations have them
         if (tg == 6 && p.otype == 6)
@@ -3289,7 +3305,17 @@ hipError_t launch_census(const sspp_job* j, int M, unsigned long long seed, unsi
     if (pairs) { T.pairs = pairs; T.visit = nullptr; }  // the asynchronous pre-pass's own copy of the sampled table
     const int r0 = std::min(P, j->n), r1 = std::max(r0, j->n - P);
     const size_t lds = sizeof(double) * ((size_t)j->n * D + (size_t)(r1 - r0) * D + D);
-    if (NM == 1 && sc.onegeom && sc.npairs > 0)
+    const bool og = NM == 1 && sc.onegeom && sc.npairs > 0;
+    if (sc.cylbox & kTableCapsule) {  // capsule pairs: the instantiations that carry their colliders
+        if (og)
+            hipLaunchKernelGGL((k_sspp_census<D, 1, P, true, true>), dim3(M), dim3(kCensusThreads), lds, st, sc, T,
+                               j->n, j->W, j->sampler, j->sigma, seed, j->d_tab, j->d_span, j->d_init, j->d_limits,
+                               d_hits);
+        else
+            hipLaunchKernelGGL((k_sspp_census<D, NM, P, false, true>), dim3(M), dim3(kCensusThreads), lds, st, sc, T,
+                               j->n, j->W, j->sampler, j->sigma, seed, j->d_tab, j->d_span, j->d_init, j->d_limits,
+                               d_hits);
+    } else if (og)
         hipLaunchKernelGGL((k_sspp_census<D, 1, P, true>), dim3(M), dim3(kCensusThreads), lds, st, sc, T, j->n, j->W,
                            j->sampler, j->sigma, seed, j->d_tab, j->d_span, j->d_init, j->d_limits, d_hits);
     else

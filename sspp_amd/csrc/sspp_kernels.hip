@@ -653,7 +653,7 @@ static void table_flags(const sspp_scene* sc, const std::vector<DPair>& t, int* 
     *og = 1;
     for (const DPair& pr : t) {
         const int tg = sc->geoms[pr.gm].type;
-        *cb |= (tg == 5 && pr.otype == 6) || (tg == 6 && pr.otype == 5);
+        *cb |= sspk::table_bits(tg, pr.otype);
         *og &= pr.gm == t[0].gm;
     }
 }
@@ -1287,7 +1287,8 @@ extern "C" int sspp_job_get_option(const sspp_job* j, int key, int64_t* value) {
         case SSPP_OPT_WP_ORDER: *value = j->wp_order; return SSPP_OK;
         case SSPP_OPT_PREPASS_US: *value = (int64_t)(j->prepass_ms * 1e3); return SSPP_OK;
         case SSPP_OPT_NPAIRS: *value = j->np_samp; return SSPP_OK;
-        case SSPP_OPT_CYLBOX: *value = j->cb_samp; return SSPP_OK;
+        case SSPP_OPT_CYLBOX: *value = (j->cb_samp & sspk::kTableCylBox) != 0; return SSPP_OK;
+        case SSPP_OPT_CAPSULE: *value = (j->cb_samp & sspk::kTableCapsule) != 0; return SSPP_OK;
         case SSPP_OPT_F32: *value = j->f32; return SSPP_OK;
         case SSPP_OPT_LAST_F32: *value = j->last_f32; return SSPP_OK;
         case SSPP_OPT_CREATE_US: *value = (int64_t)(j->create_ms * 1e3); return SSPP_OK;
