@@ -282,7 +282,7 @@ static void or_sincospi(double x, double* s, double* c) {
 
 /* FP64 Box-Muller, the default normals of both planners (reference: std::normal_distribution
    <double>, include/sspp.h:116,125 and include/sspp/tsp_sampler.h:17): the kernels' normal_pair
-   (sspp_amd/csrc/sspp_kern.h) operation for operation — ln u1 division-free: k = round(64 m),
+   (sspp_amd/csrc/sspp_rng.h) operation for operation — ln u1 division-free: k = round(64 m),
    r = RN(64/k) and -ln r = hi + lo from the shared data table (sspp_amd/csrc/sspp_logtab.h,
    generated by tools/gen_log_table.py and checked entry by entry in
    tests/test_oracle_golden.py::test_log_table), t = fma(m, r, -1), ln(1 + t) by its series to

@@ -1,5 +1,7 @@
 // sspp_kern.h — the MI355X (gfx950) candidate-scoring kernels and their launch templates.
 //
+// The profiling hooks (sspp_prof.h), the build-time knobs (sspp_knobs.h), the dynamic LDS layouts
+// (sspp_lds.h) and the random numbers (sspp_rng.h) have headers of their own.
 // Included by sspp_kernels.hip (host side: scenes, jobs, the C ABI) and by sspp_inst.hip,
 // which the Makefile compiles once per dof (-DSSPK_D=1,2,3,4,6,7,9) and once for the
 // TaskSpacePlanner kernels (-DSSPK_D=0), each explicitly instantiating its entry points, so the
@@ -28,47 +30,23 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "model.h"
-// k_tsp forms (bit f = form f) that run several sub-batches per workgroup (SSPP_OPT_TSP_REP)
-#ifndef SSPP_TSP_REP_FORMS
-#define SSPP_TSP_REP_FORMS (1 << 3)
-#endif
-#ifdef SSPP_TSP_STATS  // profiling builds only: point_collide's pair work (tools/tsp_stats.py)
-__device__ unsigned long long g_tsp_stats[16];
-#define TSP_STAT(i, c) do { const unsigned long long m_ = __ballot(c), a_ = __ballot(1);                  \
-        if (__lane_id() == __builtin_ctzll(a_) && m_) atomicAdd(&g_tsp_stats[i], (unsigned long long)__popcll(m_)); } while (0)
-#else
-#define TSP_STAT(i, c) do { } while (0)
-#endif
-#ifdef SSPP_C2F_STATS  // profiling builds only (tools/build_variant.sh stats -DSSPP_C2F_STATS)
-__device__ unsigned long long g_c2f_stats[16];
-#define SSPP_CB_STAT(i) atomicAdd(&g_c2f_stats[i], 1ull)
-#endif
-#ifdef SSPP_WG_TIMING  // profiling builds only: per-workgroup (start, end, CU, survivors) of k_sspp_c2f
-__device__ unsigned long long g_wg_t[1 << 18];
-__device__ unsigned long long g_wg_ph[8 << 16];  // per workgroup: shader clock after each phase
-#define WG_PH(k) do { if (threadIdx.x == 0 && blockIdx.x < (1 << 16)) g_wg_ph[8 * blockIdx.x + (k)] = clock64(); } while (0)
-__device__ unsigned long long g_p2_t[8 << 12];  // split launch: [4095] the last arriver's epilogue (start, end, grid)
-__device__ unsigned long long g_p2_w[8 << 13];  // split launch per queue slot: start, end (wall), passes, FP64 passes, feasible, p2/p3 clocks, wave
-#else
-#define WG_PH(k) do { } while (0)
-#endif
+#include "sspp_prof.h"
+#include "sspp_knobs.h"
+#include "sspp_lds.h"
 #include "sspp_device.h"
 #include "sspp_filter.h"
 #include "sspp_logtab.h"
+#include "sspp_rng.h"
 
 using namespace sspd;
 
 namespace sspk {
 
-constexpr int kBlock = 256;
-#ifndef SSPP_SCORE_WAVES_PER_EU
-#define SSPP_SCORE_WAVES_PER_EU 4  // min waves per SIMD (4 -> <=128 VGPRs; measured best on gfx950)
-#endif
 constexpr int kMaxMovers = 2;
-constexpr int kMaxSteps = 64;  // steps per launch (k_sspp_c2f)
 
 // what a pair contributes to its table's kernel selection (KScene::cylbox, sspp_job::cb_*)
 constexpr int kTableCylBox = 1, kTableCapsule = 2;
@@ -251,198 +229,6 @@ struct TspK {
     int rep;                // k_tsp: sub-batches of cpb candidates per workgroup (tsp_rep)
 };
 
-// ---------------------------------------------------------------- Philox4x32-10 + Box-Muller
-__device__ __forceinline__ void philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3,
-                                       unsigned k0, unsigned k1, unsigned o[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-        // one 32 x 32 -> 64-bit multiply per product (v_mad_u64_u32): hi and lo together
-        const unsigned long long p0 = (unsigned long long)c0 * 0xD2511F53u;
-        const unsigned long long p1 = (unsigned long long)c2 * 0xCD9E8D57u;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        c0 = n0; c1 = (unsigned)p1; c2 = n2; c3 = (unsigned)p0;
-    }
-    o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
-}
-__device__ __forceinline__ void philox_words(unsigned long long seed, unsigned long long g,
-                                             unsigned idx, unsigned stream, unsigned o[4]) {
-    philox(idx, stream, (unsigned)g, (unsigned)(g >> 32), (unsigned)seed, (unsigned)(seed >> 32), o);
-}
-// FP64 Box-Muller (the default sampler of both planners; std::normal_distribution<double> in the
-// reference, include/sspp.h:116,125 and include/sspp/tsp_sampler.h:17): one Philox4x32-10 call
-// gives two 53-bit uniforms u1 in (0, 1], u2 in [0, 1) -> z0 = r cos(2 pi u2), z1 = r sin(2 pi u2),
-// r = sqrt(-2 ln u1), |z| <= 8.57.  ln and sincos are written out as FP64 polynomials with
-// explicit fma (sin / cos: Taylor on |a| <= pi/4 to a^17 / a^16), an IEEE sqrt, and no division:
-// ln u = e ln 2 + ln m with m = k/64 (1 + t), k = round(64 m) — a 64-entry table (sspp_logtab.h,
-// tools/gen_log_table.py) holds r = RN(64/k) and -ln r as hi + lo, t = fma(m, r, -1) is one
-// rounding with |t| <= 2^-7, and ln(1 + t) is its series to t^8 (remainder < 2e-20).  m near 2
-// takes the next exponent's entry k = 64 (r = 1, t = m/2 - 1 exact), so ln u keeps its relative
-// precision as u -> 1.  (Round 5 computed ln m by the atanh series of s = (m-1)/(m+1), an IEEE
-// FP64 division: v_div_scale x2, v_rcp_f64, four fma, v_div_fmas / fixup per pair.)
-// oracle/sspp_oracle.c::or_normal_pair reproduces every normal bit for bit.
-__device__ __forceinline__ double bm_log64(double u) {  // ln u, u in [2^-53, 1]
-    static const double tab[64][4] = {SSPP_LOGTAB_ENTRIES};
-    const unsigned long long bits = (unsigned long long)__double_as_longlong(u);
-    const unsigned long long mb = bits & 0x000fffffffffffffull;
-    int e = (int)(bits >> 52) - 1023;
-    int k = (int)((mb + (1ull << 45)) >> 46);  // round(64 m) - 64, 0..64
-    double m = __longlong_as_double((long long)(mb | 0x3ff0000000000000ull));
-    if (k == 64) { k = 0; e += 1; m = m * 0.5; }  // m in [2 - 2^-7, 2): its half, next to 1
-    const double t = fma(m, tab[k][0], -1.0);     // m r - 1
-    const double t2 = t * t;
-    double p = -0.125;                             // -1/8
-    p = fma(t, p, 0x1.2492492492492p-3);           // 1/7
-    p = fma(t, p, -0x1.5555555555555p-3);          // -1/6
-    p = fma(t, p, 0x1.999999999999ap-3);           // 1/5
-    p = fma(t, p, -0.25);                          // -1/4
-    p = fma(t, p, 0x1.5555555555555p-2);           // 1/3
-    p = fma(t, p, -0.5);                           // -1/2
-    const double l1 = fma(t2, p, t);               // ln(1 + t)
-    const double de = (double)e;                   // ln 2 = hi + lo (hi: 42 bits, e hi exact)
-    const double hi = fma(de, 0x1.62e42fefa3800p-1, tab[k][1]);
-    const double lo = fma(de, 0x1.ef35793c76730p-45, tab[k][2]) + l1;
-    return hi + lo;
-}
-__device__ __forceinline__ void bm_sincos2pi64(double u, double* sn, double* cs) {  // u in [0, 1)
-    const double q = rint(4.0 * u);
-    const double r = fma(-0.25, q, u);         // exact, |r| <= 1/8
-    const double a = r * 0x1.921fb54442d18p+2; // 2 pi r, |a| <= pi/4
-    const double a2 = a * a;
-    double sp = 0x1.952c77030ad4ap-49;         // 1/17!
-    sp = fma(a2, sp, -0x1.ae7f3e733b81fp-41);
-    sp = fma(a2, sp, 0x1.6124613a86d09p-33);
-    sp = fma(a2, sp, -0x1.ae64567f544e4p-26);
-    sp = fma(a2, sp, 0x1.71de3a556c734p-19);
-    sp = fma(a2, sp, -0x1.a01a01a01a01ap-13);
-    sp = fma(a2, sp, 0x1.1111111111111p-7);
-    sp = fma(a2, sp, -0x1.5555555555555p-3);   // -1/3!
-    const double sa = fma(a * a2, sp, a);
-    double cp = 0x1.ae7f3e733b81fp-45;         // 1/16! (the a^18 term: < 2.1e-18 on |a| <= pi/4)
-    cp = fma(a2, cp, -0x1.93974a8c07c9dp-37);
-    cp = fma(a2, cp, 0x1.1eed8eff8d898p-29);
-    cp = fma(a2, cp, -0x1.27e4fb7789f5cp-22);
-    cp = fma(a2, cp, 0x1.a01a01a01a01ap-16);
-    cp = fma(a2, cp, -0x1.6c16c16c16c17p-10);
-    cp = fma(a2, cp, 0x1.5555555555555p-5);
-    cp = fma(a2, cp, -0x1.0000000000000p-1);   // -1/2!
-    const double ca = fma(a2, cp, 1.0);
-    const int qi = (int)q & 3;
-    *sn = qi == 0 ? sa : (qi == 1 ? ca : (qi == 2 ? -sa : -ca));
-    *cs = qi == 0 ? ca : (qi == 1 ? -sa : (qi == 2 ? -ca : sa));
-}
-__device__ __forceinline__ void normal_pair(unsigned long long seed, unsigned long long g,
-                                            unsigned idx, unsigned stream, double* z0, double* z1) {
-    unsigned o[4];
-    philox_words(seed, g, idx, stream, o);
-    const unsigned long long a = ((((unsigned long long)o[0]) << 32) | o[1]) >> 11;
-    const unsigned long long b = ((((unsigned long long)o[2]) << 32) | o[3]) >> 11;
-    const double u1 = (double)(a + 1) * 0x1p-53;  // (0, 1], exact
-    const double u2 = (double)b * 0x1p-53;        // [0, 1), exact
-    const double r = sqrt(-2.0 * bm_log64(u1));
-    double sn, cs;
-    bm_sincos2pi64(u2, &sn, &cs);
-    *z0 = r * cs;
-    *z1 = r * sn;
-}
-// Opt-in FP32 SamplingPathPlanner normals (sspp_sspp_args::sampler = 1, the round-2 default): one
-// Philox4x32-10 call gives four 24-bit uniforms -> two Box-Muller pairs in FP32, with fmaf
-// polynomials written out (ln u by the atanh series on the mantissa, sin / cos of 2 pi u after an
-// exact quarter-turn reduction) and a correctly rounded sqrtf, so
-// oracle/sspp_oracle.c::or_normal_quad reproduces it bit for bit.  |z| <= 5.77 (u1 >= 2^-24):
-// narrower than the reference's std::normal_distribution<double>, hence not the default.
-__device__ __forceinline__ float bm_log(float u) {  // ln u, u in [2^-24, 1]
-    const unsigned bits = __float_as_uint(u);
-    int e = (int)(bits >> 23) - 127;
-    float m = __uint_as_float((bits & 0x7fffffu) | 0x3f800000u);  // [1, 2)
-    if (m > 1.41421356f) { m = m * 0.5f; e += 1; }
-    const float s = (m - 1.0f) / (m + 1.0f);                      // |s| <= 0.1716
-    const float s2 = s * s;
-    float p = fmaf(s2, 0.111111111f, 0.142857143f);
-    p = fmaf(s2, p, 0.2f);
-    p = fmaf(s2, p, 0.333333333f);
-    p = fmaf(s2, p, 1.0f);
-    return fmaf((float)e, 0.693147181f, (s + s) * p);
-}
-__device__ __forceinline__ void bm_sincos2pi(float u, float* sn, float* cs) {  // u in [0, 1)
-    const float q = rintf(4.0f * u);
-    const float r = fmaf(-0.25f, q, u);  // exact
-    const float a = r * 6.28318531f;     // |a| <= pi / 4
-    const float a2 = a * a;
-    float sp = fmaf(a2, 2.75573192e-6f, -1.98412698e-4f);
-    sp = fmaf(a2, sp, 8.33333333e-3f);
-    sp = fmaf(a2, sp, -0.166666667f);
-    const float sa = fmaf(a * a2, sp, a);
-    float cp = fmaf(a2, 2.48015873e-5f, -1.38888889e-3f);
-    cp = fmaf(a2, cp, 4.16666667e-2f);
-    cp = fmaf(a2, cp, -0.5f);
-    const float ca = fmaf(a2, cp, 1.0f);
-    const int qi = (int)q & 3;
-    *sn = qi == 0 ? sa : (qi == 1 ? ca : (qi == 2 ? -sa : -ca));
-    *cs = qi == 0 ? ca : (qi == 1 ? -sa : (qi == 2 ? -ca : sa));
-}
-__device__ __forceinline__ void normal_quad(unsigned long long seed, unsigned long long g,
-                                            unsigned idx, unsigned stream, double z[4]) {
-    unsigned o[4];
-    philox_words(seed, g, idx, stream, o);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const float u1 = (float)((o[2 * h] >> 8) + 1u) * 5.96046448e-8f;  // (0, 1], exact
-        const float u2 = (float)(o[2 * h + 1] >> 8) * 5.96046448e-8f;     // [0, 1), exact
-        const float r = sqrtf(-2.0f * bm_log(u1));
-        float sn, cs;
-        bm_sincos2pi(u2, &sn, &cs);
-        z[2 * h] = (double)(r * cs);
-        z[2 * h + 1] = (double)(r * sn);
-    }
-}
-__device__ __forceinline__ double uniform01(unsigned long long seed, unsigned long long g,
-                                            unsigned idx, unsigned stream) {
-    unsigned o[4];
-    philox_words(seed, g, idx, stream, o);
-    unsigned long long b = ((((unsigned long long)o[2]) << 32) | o[3]) >> 11;
-    return (double)b * 1.1102230246251565e-16;
-}
-
-// sampleWithNoise (include/sspp.h:114-130) in work items: item m of a candidate draws normals
-// 2m, 2m+1 (sampler 0: FP64 pair, Philox idx m) or 4m .. 4m+3 (sampler 1: FP32 quad) and adds
-// (sigma z) limits(d) to the initial spline's perturbed control-point block `base` (row-major
-// (j - p) * D + d), writing the candidate's block c: c[k] = base[k] + (sigma z_k) limits[k % D].
-__device__ __forceinline__ int sample_items(int sampler, int npert) {
-    return sampler ? (npert + 3) >> 2 : (npert + 1) >> 1;
-}
-// c32 (optional): the FP32 copy of the same values (k_sspp_c2f's filtered scan)
-__device__ __forceinline__ void sample_item_to(int sampler, unsigned long long seed, unsigned long long g,
-                                               int m, int npert, int D, double sigma,
-                                               const double* limits, const double* base, double* c,
-                                               float* c32 = nullptr) {
-    if (sampler == 0) {
-        double z0, z1;
-        normal_pair(seed, g, (unsigned)m, 0u, &z0, &z1);
-        const int k = 2 * m;
-        const double v0 = base[k] + (sigma * z0) * limits[k % D];
-        c[k] = v0;
-        if (c32) c32[k] = (float)v0;
-        if (k + 1 < npert) {
-            const double v1 = base[k + 1] + (sigma * z1) * limits[(k + 1) % D];
-            c[k + 1] = v1;
-            if (c32) c32[k + 1] = (float)v1;
-        }
-    } else {
-        double z[4];
-        normal_quad(seed, g, (unsigned)m, 0u, z);
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-            const int k = 4 * m + h;
-            if (k < npert) {
-                const double v = base[k] + (sigma * z[h]) * limits[k % D];
-                c[k] = v;
-                if (c32) c32[k] = (float)v;
-            }
-        }
-    }
-}
-
 // ---------------------------------------------------------------- spline from basis rows
 // N: p+1 basis values of one waypoint (host-precomputed table in global memory, L2 resident)
 template <int D, int P>
@@ -600,13 +386,6 @@ __device__ __forceinline__ void geom_rot_t(const double* R, const DGeom& G, doub
 // REC 4 (k_tsp<..., DEF 2>): the records of REC 3 without the terms — the lane itself sums its
 // records after the pair loop (tsp_lane_sum), recomputing each term from the recorded pose.
 constexpr int kBbPend = 16;
-#ifndef SSPP_TSP_LEAN_GEOM
-#ifdef SSPP_TSP_STATS  // (the statistics read the geom record at every pair)
-#define SSPP_TSP_LEAN_GEOM 0
-#else
-#define SSPP_TSP_LEAN_GEOM 1
-#endif
-#endif
 template <int D, int NM, int MODE, bool DEEP, bool ONEGEOM, int CB = 1, int REC = 0, bool UP = false>
 __device__ int point_collide(const double* q, const KScene& sc, const SceneT& T,
                              unsigned long long mask, double* cost, int* stop = nullptr,
@@ -971,73 +750,6 @@ __device__ __forceinline__ void finish_batch(const BlockBest bb, BlockBest* __re
 // finish_batch) picks the lowest global id at each step's minimum from that list, writes the
 // records and re-arms the queue for the next launch on the job's stream.
 constexpr unsigned long long kLingerTicksDefault = 1000000;  // 10 ms of the 100 MHz wall clock
-#ifdef SSPP_DEBUG_PROGRESS  // progress beacons of the split launch: plain stores into a [grid][8]
-// buffer (device memory for timing; mapped host memory to watch a launch that does not finish)
-#define SSPP_BEACON(B_PH, B_X, B_Y)                                                                              \
-    do {                                                                                                        \
-        if (q.beacon && threadIdx.x == 0) {                                                                     \
-            q.beacon[8 * blockIdx.x + 1] = (unsigned)(B_X);                                                     \
-            q.beacon[8 * blockIdx.x + 2] = (unsigned)(B_Y);                                                     \
-            q.beacon[8 * blockIdx.x] = (unsigned)(B_PH);                                                        \
-        }                                                                                                       \
-    } while (0)
-// wave 1's progress (thread 64) in the workgroup's fourth word
-#define SSPP_BEACON1(B_PH)                                                                                      \
-    do {                                                                                                        \
-        if (q.beacon && threadIdx.x == 64) q.beacon[8 * blockIdx.x + 3] = (unsigned)(B_PH);                    \
-    } while (0)
-// the 100 MHz wall clock's low word at a workgroup event, word 4 + B_K of its record
-#define SSPP_BEACON_T(B_K)                                                                                      \
-    do {                                                                                                        \
-        if (q.beacon && threadIdx.x == 0) q.beacon[8 * blockIdx.x + 4 + (B_K)] = (unsigned)wall_clock64();    \
-    } while (0)
-// the last workgroup's epilogue stages: word B_K after the grid's records
-#define SSPP_BEACON_E(B_K)                                                                                      \
-    do {                                                                                                        \
-        if (q.beacon && threadIdx.x == 0) q.beacon[8 * gridDim.x + (B_K)] = (unsigned)wall_clock64();          \
-    } while (0)
-#else
-#define SSPP_BEACON(B_PH, B_X, B_Y) do { } while (0)
-#define SSPP_BEACON1(B_PH) do { } while (0)
-#define SSPP_BEACON_T(B_K) do { } while (0)
-#define SSPP_BEACON_E(B_K) do { } while (0)
-#endif
-// Ready-word ordering.  Every access to the queue's shared data (rows, ready words, counters)
-// is an agent-scope atomic (global_load / global_store ... sc1: coherent across the XCDs, not
-// held in a non-coherent cache level), and the protocol orders them with s_waitcnt: the producer
-// waits for its row stores to complete (vmcnt(0), each thread, then the workgroup barrier)
-// before it stores the ready word, and the consumer issues its row loads only after its load of
-// the word has returned.  That is the hardware ordering of CDNA4 for sc1 accesses.  The C++
-// release / acquire pair (SSPP_QUEUE_FENCES 1) compiles to buffer_wbl2 sc1 (write back this
-// XCD's whole L2) before each word store and buffer_inv sc1 (invalidate it) after each word
-// load: 49.4 -> 73.4 us per 20-step launch (profiles/r06d_*), for data that never passes
-// through those caches.  It stays a build option (tools/runs, A/B); the default is the
-// relaxed form.
-#ifndef SSPP_QUEUE_FENCES
-#define SSPP_QUEUE_FENCES 0
-#endif
-#if SSPP_QUEUE_FENCES
-#define SSPP_QUEUE_RELEASE_ORDER __ATOMIC_RELEASE
-#define SSPP_QUEUE_ACQUIRE() __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent")
-#else
-#define SSPP_QUEUE_RELEASE_ORDER __ATOMIC_RELAXED
-#define SSPP_QUEUE_ACQUIRE() do { } while (0)
-#endif
-#ifndef SSPP_SPLIT_PRIO  // split launches: issue priority by phase (s_setprio; A/B: 0)
-#define SSPP_SPLIT_PRIO 1
-#endif
-#ifndef SSPP_PRIO_ALL  // the same priorities in the unsplit instances (A/B)
-#define SSPP_PRIO_ALL 0
-#endif
-#ifndef SSPP_SPLIT_PRIO_CONSUMER  // the priority of a wave past phase 1 (push, queued survivors)
-#define SSPP_SPLIT_PRIO_CONSUMER 0
-#endif
-#ifndef SSPP_QUEUE_WAITERS  // tickets per shard that may wait for slots not reserved yet
-#define SSPP_QUEUE_WAITERS 4
-#endif
-#ifndef SSPP_LINGER_SLEEP  // s_sleep between a waiting wave's polls (x 64 clocks)
-#define SSPP_LINGER_SLEEP 16
-#endif
 constexpr int kSurvShards = 64;      // queue shards: workgroup b produces into and consumes from b % 64
 struct SurvShard {
     unsigned count;                    // slots reserved by the shard's producers
@@ -1119,12 +831,6 @@ struct SsppC2F {
                                  // handed-over tickets, which the lost-work check must report
     unsigned long long linger;   // wall-clock ticks a ticket waits before it is handed over
 };
-
-#ifdef SSPP_C2F_STATS
-#define C2F_STAT(i, v) do { const unsigned long long v_ = (v); if ((threadIdx.x & 63) == 0 && v_) atomicAdd(&g_c2f_stats[i], v_); } while (0)
-#else
-#define C2F_STAT(i, v) do { } while (0)
-#endif
 
 // LDS offset (in doubles) of control-point row j of a candidate whose own rows [r0, r1) start at
 // `mine`; the other rows are the workgroup's shared copy of the initial spline at `fix`.
@@ -1407,6 +1113,15 @@ __device__ __forceinline__ unsigned long long wave_or64(unsigned long long m) {
            (unsigned)__builtin_amdgcn_readfirstlane((int)lo);
 }
 
+// One wave (tid < 64) compacts its lanes' values into an LDS list, in lane order: the lanes with
+// `keep` write list[rank] = value, lane 0 the count to list[count_at].  (In place is fine: the
+// ballot follows every lane's read of its value.)
+__device__ __forceinline__ void wave_compact(int tid, bool keep, int value, int* list, int count_at) {
+    const unsigned long long m = __ballot(keep);
+    if (keep) list[__popcll(m & ((1ull << tid) - 1ull))] = value;
+    if (tid == 0) list[count_at] = __popcll(m);
+}
+
 // ================================================================ hit census (job creation)
 // The waypoint order of k_sspp_c2f's phase 1 is chosen from where sampled candidates of the
 // job's own distribution touch the scene: one workgroup per census candidate draws it
@@ -1424,9 +1139,10 @@ __global__ __launch_bounds__(kCensusThreads) void k_sspp_census(
     constexpr int P1 = P + 1;
     const int tid = threadIdx.x, m = blockIdx.x, ndof = n * D, nw = (W + 64) >> 6;
     const int r0 = P < n ? P : n, r1 = n - P > r0 ? n - P : r0, nrd = (r1 - r0) * D;
-    double* s_fix = smem;             // [n][D]
-    double* s_own = s_fix + ndof;     // [r1 - r0][D]
-    double* s_lim = s_own + nrd;      // [D]
+    const CensusLds L = census_layout(n, D, nrd);  // (sspp_lds.h)
+    double* s_fix = smem + L.fix;     // [n][D]
+    double* s_own = smem + L.own;     // [r1 - r0][D]
+    double* s_lim = smem + L.lim;     // [D]
     for (int e = tid; e < ndof; e += kCensusThreads) s_fix[e] = init_ctrl[e];
     if (tid < D) s_lim[tid] = limits[tid];
     for (int w = tid; w < nw; w += kCensusThreads) hits[(long long)m * nw + w] = 0ull;
@@ -1438,16 +1154,13 @@ __global__ __launch_bounds__(kCensusThreads) void k_sspp_census(
         const int j = j0 + tid;
         const bool live = j <= W;
         double q[D];
-        eval_split_g<D, P>(smem, ndof, 0, r0, r1, tab + (live ? j : 0) * P1, span[live ? j : 0], q);
+        eval_split_g<D, P>(smem, L.own, L.fix, r0, r1, tab + (live ? j : 0) * P1, span[live ? j : 0], q);
         bool dfr = false;
         const bool h = scan_pairs<D, NM, ONEGEOM, CAP ? 2 : 0>(q, live, ~0ull, ~0ull, 1ull << (tid & 63), nullptr, sc, T, dfr);
         if (h && live) atomicOr(hits + (long long)m * nw + (j >> 6), 1ull << (j & 63));
     }
 }
 
-#ifndef SSPP_CB_INLINE
-#define SSPP_CB_INLINE __attribute__((noinline))
-#endif
 // The exact cylinder-box test (witnesses + candidate search, sspd::cyl_box_overlap) and the
 // capsule colliders of one waypoint of one candidate over its cylinder-box and capsule pairs
 // (the pairs the scans leave undecided).  Out of line: it runs only for the
@@ -1528,10 +1241,7 @@ __device__ __forceinline__ void surv_finish(const SsppC2F& a, const SceneT& TT, 
     const int r0 = a.r0, r1 = a.r1, nch = a.W - 1;
     const int step = (int)((word >> 32) & 0xFFu), lc = (int)(unsigned)word;
     const int j0 = a.n1, R = a.npts - j0;
-#ifdef SSPP_WG_TIMING
-    const unsigned long long w_t0 = wall_clock64(), c0 = clock64();
-    unsigned w_np = 0, w_nf = 0;
-#endif
+    WG_SURV_BEGIN();
     SSPP_BEACON(20, slot, 0);
     for (int jb = 0; jb < R; jb += NT) {  // workgroup-uniform
         // a uniform exit once a pass has found a contact (every thread's read precedes the barrier)
@@ -1551,9 +1261,7 @@ __device__ __forceinline__ void surv_finish(const SsppC2F& a, const SceneT& TT, 
             h = scan_pairs32<D, NM, ONEGEOM>(q32, live, ~0ull, ~0ull, ~0ull, a.sc, TT, a.feps, a.fplim, amb);
             const bool need = live && !h && amb != 0ull;
             if (__ballot(need) != 0ull && __ballot(h) == 0ull) {  // one contact decides the survivor
-#ifdef SSPP_WG_TIMING
-                ++w_nf;
-#endif
+                WG_SURV_PASS64();
                 double qd[D];
                 bool dfr = false;
                 eval_split_g<D, P>(smem, o_own, o_fix, r0, r1, otab + j * P1, ospan[j], qd);
@@ -1567,17 +1275,13 @@ __device__ __forceinline__ void surv_finish(const SsppC2F& a, const SceneT& TT, 
             h = scan_pairs<D, NM, ONEGEOM>(qd, live, ~0ull, ~0ull, ~0ull, nullptr, a.sc, TT, dfr);
         }
         if (__ballot(h) != 0ull && lane == 0) __hip_atomic_store(s_ctl, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#ifdef SSPP_WG_TIMING
-        ++w_np;
-#endif
+        WG_SURV_PASS();
     }
     SSPP_BEACON(21, slot, 0);
     __syncthreads();
     const bool feas = __builtin_amdgcn_readfirstlane(s_ctl[0]) != 0;
     SSPP_BEACON(22, slot, feas);
-#ifdef SSPP_WG_TIMING
-    const unsigned long long c1 = clock64();
-#endif
+    WG_SURV_P2_DONE();
     double total = INFINITY;
     if (feas) {
         // phase 3: lane partials over lpc lanes, xor butterfly per 64-lane group, groups in order
@@ -1620,48 +1324,19 @@ __device__ __forceinline__ void surv_finish(const SsppC2F& a, const SceneT& TT, 
             }
             if (feas) __hip_atomic_fetch_add(q.hdr->count_feas + step, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-#ifdef SSPP_WG_TIMING
-        unsigned long long* t = g_p2_w + 8 * (slot & ((8u << 10) - 1u));
-        t[0] = w_t0; t[1] = wall_clock64(); t[2] = w_np; t[3] = w_nf; t[4] = feas;
-        t[5] = c1 - c0; t[6] = clock64() - c1; t[7] = blockIdx.x;
-#endif
+        WG_SURV_RECORD(slot, feas);
     }
     (void)slot;
     SSPP_BEACON(24, slot, 0);
     __syncthreads();  // the next survivor may overwrite the rows and the flags
 }
 
-// Occupancy per shape: one- and two-wave workgroups of a single-geom mover at 5 waves per SIMD
-// (96 VGPRs: 20 waves per CU, so the 20-step launch of 4096-candidate steps at 128 x 4 is one
-// resident round); 4-wave workgroups and multi-geom movers at 4 (128 VGPRs; at 5 they spill).
-// Round 6 (tools/kres.py, profiles/r06pmc_*): the robocrane d7 instances at 128 threads spill
-// no VGPR, split and unsplit; the split one has no scratch at all (Registers).
-#ifndef SSPP_C2F_WAVES_PER_EU
-#define SSPP_C2F_WAVES_PER_EU 5
-#endif
-#ifndef SSPP_C2F_WAVES_PER_EU_WIDE
-#define SSPP_C2F_WAVES_PER_EU_WIDE 4
-#endif
-// Workgroups of up to 128 threads run at SSPP_C2F_WAVES_PER_EU (96 VGPRs); the 256-thread
-// latency shape carries the phase-2 pair groups (few survivor items over many lanes), which
-// cost registers (at 5 waves per SIMD they spill), and runs at SSPP_C2F_WAVES_PER_EU_WIDE.
-// profiling builds only (tools/build_variant.sh -DSSPP_ABLATE=mask): 1 no sampling, 2 no
-// collision, 4 no arc, 8 no phase 2, 16 no phase 1, 64 return at entry (launch cost only)
-#ifndef SSPP_ABLATE
-#define SSPP_ABLATE 0
-#endif
 // CBX: the pair table has cylinder-box or capsule pairs, so the kernel carries the settle step (its
 // out-of-line exact test costs the whole kernel registers: 96 -> 128 VGPRs and scratch)
 // SPLIT: the split launch's instance (single-geom movers without cylinder-box pairs): phase 1,
 // then the survivor queue; the in-workgroup phases 2-4 are unreachable there and compiled out, so
 // the queue costs the unsplit instances no registers
 template <int D, int NM, int P, bool ONEGEOM, int NT, bool CBX, bool SPLIT = false>
-#ifndef SSPP_C2F_FIVE_MAX  // profiling builds: the largest workgroup at SSPP_C2F_WAVES_PER_EU
-#define SSPP_C2F_FIVE_MAX 128
-#endif
-#ifndef SSPP_C2F_GP_NT     // profiling builds: the workgroup size that carries the pair groups
-#define SSPP_C2F_GP_NT 256
-#endif
 __global__ __launch_bounds__(NT, (NT <= SSPP_C2F_FIVE_MAX && ONEGEOM) ? SSPP_C2F_WAVES_PER_EU : SSPP_C2F_WAVES_PER_EU_WIDE) void k_sspp_c2f(
     SsppC2F a, SceneT T, const double* __restrict__ otab, const float* __restrict__ otab32,
     const int* __restrict__ ospan,
@@ -1688,10 +1363,7 @@ __global__ __launch_bounds__(NT, (NT <= SSPP_C2F_FIVE_MAX && ONEGEOM) ? SSPP_C2F
     // oldest waves: at 5 waves per SIMD the first-dispatched waves finished phase 1 at ~12 us and
     // the last at ~25-36 us (profiles/r06c_beacons*), whose survivors then formed the launch's tail
     if constexpr ((SPLIT || SSPP_PRIO_ALL) && SSPP_SPLIT_PRIO) __builtin_amdgcn_s_setprio(2);
-#ifdef SSPP_WG_TIMING
-    const unsigned long long wg_t0 = wall_clock64();
-    int wg_ns = -1;
-#endif
+    WG_T_BEGIN();
     WG_PH(0);
     double* const arc_base = arc;  // the split launch's consumers write any step's outputs
     unsigned char* const feas_base = feasible;
@@ -1706,6 +1378,9 @@ __global__ __launch_bounds__(NT, (NT <= SSPP_C2F_FIVE_MAX && ONEGEOM) ? SSPP_C2F
     }
     // LDS (doubles): the shared initial spline [n][D], the candidates' own rows [cpb][r1-r0][D],
     // the limits [D], then the hull boxes (phase 2) — reused by phase 3's sums — and the flags
+    // (formed by hand: taking these pointers from a layout struct moved the kernel's register
+    // allocation.  C2fLds in sspp_lds.h restates this chain for the host's byte count; nothing
+    // checks the two against each other, so an edit here is an edit there)
     const int o_fix = 0, o_own = ndof;
     double* s_lim = smem + o_own + cpb * nrd;                 // [D] sampleWithNoise limits
     const int nvw3 = a.lpc >> 6, rbox = 2 * NB > nvw3 + 1 ? 2 * NB : nvw3 + 1;
@@ -1891,9 +1566,7 @@ __global__ __launch_bounds__(NT, (NT <= SSPP_C2F_FIVE_MAX && ONEGEOM) ? SSPP_C2F
         bool last = false;        // workgroup-uniform: the launch's last workgroup, on the hand-over list
         unsigned ko = 0, no = 0;  // (thread 0) position in the hand-over list, its length
         unsigned handed = 0;      // (thread 0) this workgroup handed a ticket over (it then leaves)
-#ifdef SSPP_DEBUG_PROGRESS
-        unsigned nfin = 0;        // (thread 0) survivors this workgroup finished (beacon word 3)
-#endif
+        SSPP_BEACON_FIN_DECL();   // (thread 0) survivors this workgroup finished (beacon word 3)
         for (;;) {  // workgroup-uniform (the slot and word come from LDS through readfirstlane)
             if (tid == 0) {
                 unsigned t = ~0u;
@@ -1979,14 +1652,7 @@ __global__ __launch_bounds__(NT, (NT <= SSPP_C2F_FIVE_MAX && ONEGEOM) ? SSPP_C2F
             const unsigned t = (unsigned)__builtin_amdgcn_readfirstlane(s_ctl[1]);
             if (t == ~0u) {
                 if (last) break;
-#ifdef SSPP_WG_TIMING
-                if (tid == 0 && blockIdx.x < (1 << 16)) {
-                    g_wg_t[4 * blockIdx.x] = wg_t0;
-                    g_wg_t[4 * blockIdx.x + 1] = wall_clock64();
-                    g_wg_t[4 * blockIdx.x + 2] = __smid();
-                    g_wg_t[4 * blockIdx.x + 3] = 0ull;
-                }
-#endif
+                WG_T_RECORD(tid, 0ull);
                 SSPP_BEACON(8, 0, 0);
                 SSPP_BEACON_T(3);
                 // ---- completion: sharded arrival; the last workgroup goes on with the hand-over list.
@@ -2032,19 +1698,16 @@ __global__ __launch_bounds__(NT, (NT <= SSPP_C2F_FIVE_MAX && ONEGEOM) ? SSPP_C2F
             if (tid == 0)
                 __hip_atomic_fetch_add(&q.hdr->shard[t / (unsigned)q.shard_cap].served, 1u, __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_AGENT);
-#ifdef SSPP_DEBUG_PROGRESS
-            if (tid == 0 && q.beacon) q.beacon[8 * blockIdx.x + 3] = ++nfin;
-#endif
+            SSPP_BEACON_FIN(tid);
         }
-#ifdef SSPP_WG_TIMING
-        const unsigned long long t_ep = wall_clock64();
-#endif
+        WG_EP_BEGIN();
         // the last workgroup: every handed-over slot is finished
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the outputs, list entries and counts
         __syncthreads();
         SSPP_BEACON(12, no, 0);
         SSPP_BEACON_E(1);
         // LDS is free: the per-step minimum bits, ids and feasible counts, the lost survivors
+        // (formed by hand; C2fSplitLds in sspp_lds.h restates it for the host's byte count: keep them equal)
         int tid_e = threadIdx.x;
         asm volatile("" : "+v"(tid_e));  // (as at the producer: no offsets held across the queue)
         const int tid_ep = tid_e;
@@ -2128,11 +1791,7 @@ __global__ __launch_bounds__(NT, (NT <= SSPP_C2F_FIVE_MAX && ONEGEOM) ? SSPP_C2F
             __hip_atomic_store(&q.hdr->lost, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(&q.hdr->norphan, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             SSPP_BEACON(13, (unsigned)wall_clock64(), lost);
-#ifdef SSPP_WG_TIMING
-            g_p2_t[8 * 4095] = t_ep;
-            g_p2_t[8 * 4095 + 1] = wall_clock64();
-            g_p2_t[8 * 4095 + 2] = gridDim.x;
-#endif
+            WG_EP_RECORD();
         }
         return;
     }
@@ -2140,28 +1799,17 @@ __global__ __launch_bounds__(NT, (NT <= SSPP_C2F_FIVE_MAX && ONEGEOM) ? SSPP_C2F
     const int j0 = a.n1;
     const int R = a.npts - j0;
     if (collide_on && R > 0 && !(ABL & 8)) {
-        if (tid < 64) {  // survivors compacted by one wave ballot (cpb <= 64), in candidate order
-            const bool f = tid < nvalid && s_feas[tid] != 0;
-            const unsigned long long m = __ballot(f);
-            if (f) s_surv[__popcll(m & ((1ull << tid) - 1ull))] = tid;
-            if (tid == 0) s_surv[cpb] = __popcll(m);
-        }
+        // survivors compacted by one wave ballot (cpb <= 64), in candidate order
+        if (tid < 64) wave_compact(tid, tid < nvalid && s_feas[tid] != 0, tid, s_surv, cpb);
         __syncthreads();
         int ns = s_surv[cpb];
         if (tid == 0) C2F_STAT(6, ns);
-#ifdef SSPP_WG_TIMING
-        wg_ns = ns;
-#endif
+        WG_T_SURVIVORS(ns);
         // the survivors' hull masks: AABB of the control points per (survivor, mover, axis),
         // then one (survivor, pair) test per thread (pair_may_touch; exact, see above).  Only
         // survivors: phase 1 stops at the first touching pair anyway, and computing the masks
-        // for every candidate cost more than it saved (robocrane: 1.11 vs 1.22 G cand/s)
-        // with 8 pairs or fewer the masks cull too little to pay for their two barriers and the
-        // hull pass: robocrane (4 pairs) kernel 54.9 -> 53.7 us at 20 steps, 79.9 -> 78.1 us at
-        // 1000 (profiles/r04aa_mask_ab.txt); the scan tests every pair exactly either way
-#ifndef SSPP_P2_MASK_MIN
-#define SSPP_P2_MASK_MIN 9
-#endif
+        // for every candidate cost more than it saved (robocrane: 1.11 vs 1.22 G cand/s); and
+        // only from SSPP_P2_MASK_MIN pairs on (sspp_knobs.h)
         const bool hull = np <= 64 && np >= SSPP_P2_MASK_MIN;  // otherwise every pair is scanned
         if (ns > 0 && hull) {
             for (int e = tid; e < ns * NB; e += NT) {
@@ -2205,10 +1853,7 @@ __global__ __launch_bounds__(NT, (NT <= SSPP_C2F_FIVE_MAX && ONEGEOM) ? SSPP_C2F
                 __syncthreads();  // this round's flag updates are visible
                 if (tid < 64) {   // in-place compaction by one wave (reads precede the writes)
                     const int s = tid < ns ? s_surv[tid] : 0;
-                    const bool f = tid < ns && s_feas[s] != 0;
-                    const unsigned long long m = __ballot(f);
-                    if (f) s_surv[__popcll(m & ((1ull << tid) - 1ull))] = s;
-                    if (tid == 0) s_surv[cpb] = __popcll(m);
+                    wave_compact(tid, tid < ns && s_feas[s] != 0, s, s_surv, cpb);
                 }
                 __syncthreads();
                 ns = __builtin_amdgcn_readfirstlane(s_surv[cpb]);
@@ -2294,12 +1939,7 @@ __global__ __launch_bounds__(NT, (NT <= SSPP_C2F_FIVE_MAX && ONEGEOM) ? SSPP_C2F
     // test at every collision waypoint (the OR over waypoints and pairs is unchanged)
     if (CBX && collide_on) {
         __syncthreads();
-        if (tid < 64) {
-            const bool u = tid < nvalid && s_feas[tid] != 0 && s_defer[tid] != 0;
-            const unsigned long long m = __ballot(u);
-            if (u) s_surv[__popcll(m & ((1ull << tid) - 1ull))] = tid;
-            if (tid == 0) s_surv[cpb] = __popcll(m);
-        }
+        if (tid < 64) wave_compact(tid, tid < nvalid && s_feas[tid] != 0 && s_defer[tid] != 0, tid, s_surv, cpb);
         __syncthreads();
         const int nu = s_surv[cpb];
         for (int i = 0; i < nu; ++i) {  // workgroup-uniform
@@ -2321,12 +1961,8 @@ __global__ __launch_bounds__(NT, (NT <= SSPP_C2F_FIVE_MAX && ONEGEOM) ? SSPP_C2F
     if (!(ABL & 4)) {
         __syncthreads();
         int* s_list = s_surv;  // phase 2 is done with it
-        if (tid < 64) {  // one wave ballot, candidate order
-            const bool f = tid < nvalid && (a.arc_all || s_feas[tid] != 0);
-            const unsigned long long m = __ballot(f);
-            if (f) s_list[__popcll(m & ((1ull << tid) - 1ull))] = tid;
-            if (tid == 0) s_list[cpb] = __popcll(m);
-        }
+        // one wave ballot, candidate order
+        if (tid < 64) wave_compact(tid, tid < nvalid && (a.arc_all || s_feas[tid] != 0), tid, s_list, cpb);
         __syncthreads();
         const int nl = s_list[cpb];
         // one wave per (listed candidate, 64-lane group v of the lpc canonical lanes): lane l
@@ -2395,25 +2031,12 @@ __global__ __launch_bounds__(NT, (NT <= SSPP_C2F_FIVE_MAX && ONEGEOM) ? SSPP_C2F
     }
     finish_batch<NT>(bb, part, sync, best, a.nblk_step, blk);
     WG_PH(6);
-#ifdef SSPP_WG_TIMING
-    if (tid == 0 && blockIdx.x < (1 << 16)) {
-        g_wg_t[4 * blockIdx.x] = wg_t0;
-        g_wg_t[4 * blockIdx.x + 1] = wall_clock64();
-        g_wg_t[4 * blockIdx.x + 2] = __smid();
-        g_wg_t[4 * blockIdx.x + 3] = (unsigned long long)(long long)wg_ns;
-    }
-#endif
+    WG_T_RECORD(tid, WG_T_NS);
 }
 
 // ---------------------------------------------------------------- TaskSpacePlanner kernel
 // tab: (cp+1) rows of 3 basis values at u = i * (1/cp); Minv: the collocation matrix's QR
 // program (spline_host.cpp qr_program: [n][n] reflectors | [n] |v|^2 | [n][n] R).
-#ifndef SSPP_TSP_WAVES_PER_EU
-#define SSPP_TSP_WAVES_PER_EU 3
-#endif
-#ifndef SSPP_TSP_WAVES_PER_EU_CB  // with the exact cylinder-box test (its live state doubles)
-#define SSPP_TSP_WAVES_PER_EU_CB 2
-#endif
 // The per-problem values of a TaskSpacePlanner launch: a k_tsp launch's own (TspK), or one goal's
 // of a multi-goal launch (k_tsp_group, TspGoals)
 struct TspVar {
@@ -2559,25 +2182,12 @@ __device__ __forceinline__ void tsp_prologue(const TspK& a, const TspVar& pv, co
 
 // CB: the scene has cylinder-box pairs (without them the exact cylinder-box code is compiled
 // out: it costs registers even when it never runs)
-// Several moving geoms (the gripper's 7): 3 waves per SIMD, 168 VGPRs with ~50 spilled, beats
-// 2 waves without spills (multi-goal 40.6 against 34.6 M cand/s; 4 waves: 29.8)
-#ifndef SSPP_TSP_WAVES_PER_EU_MG
-#define SSPP_TSP_WAVES_PER_EU_MG 3
-#endif
 // DEF (one waypoint per lane, at most kDefPairs pairs): box-box contact polygons deferred — the
 // waypoint loop records every pair's count / term (REC 3), the workgroup then counts the
 // polygons of its compacted deep box-box pairs (all lanes busy, instead of the lanes of each
 // wave that happen to hold one), and each lane sums its records in pair order: the same additions
 // in the same order as the inline form, so the costs are bit-identical.
 constexpr int kDefPairs = 8;
-#ifndef SSPP_TSP_SUB_LAUNDER
-#define SSPP_TSP_SUB_LAUNDER 1
-#endif
-// 4 waves per SIMD, no spills.  5 waves (96 VGPRs, ~75 spilled) measured 106.0 against 101.6 M
-// cand/s on stacking, but its spills raised the HBM traffic from 1.4x to 140x the algorithmic bytes
-#ifndef SSPP_TSP_WAVES_PER_EU_DEF
-#define SSPP_TSP_WAVES_PER_EU_DEF 4
-#endif
 // k_tsp's body: workgroup blk of a problem (k_tsp: the launch's; k_tsp_group: a goal's)
 template <int NM, bool ONEGEOM, int CB, bool UP, int DEF>
 __device__ __forceinline__ void tsp_body(
@@ -2858,11 +2468,11 @@ __global__ __launch_bounds__(64 * G, 2) void k_tsp_pp(
     const int tid = threadIdx.x, n = a.n, cp = a.cp, np = a.sc.npairs;
     const int g = tid >> 6, lane = tid & 63;
     const long long cand0 = blockIdx.x;
-    const int ndof = n * D;
+    const TspPpLds L = tsp_pp_layout(n, true);  // (sspp_lds.h)
     double* s_V = smem;                       // [n][4]
-    double* s_ctrl = s_V + ndof;              // [n][4]
-    double* s_term = s_ctrl + ndof;           // [64 waypoints][64 pairs]
-    unsigned char* s_nd = (unsigned char*)(s_term + 64 * 64);  // [64][64]
+    double* s_ctrl = s_V + L.n_V;             // [n][4]
+    double* s_term = s_ctrl + L.n_ctrl;       // [64 waypoints][64 pairs]
+    unsigned char* s_nd = (unsigned char*)(s_term + L.n_term);  // [64][64]
     const long long nvalid = 1;
     const long long nfx = a.ces ? (long long)*a.nfixed : 0;
     for (int e = tid; e < 64 * 64 / 4; e += NT) ((unsigned*)s_nd)[e] = 0u;
@@ -2954,9 +2564,9 @@ __global__ __launch_bounds__(64 * G, 2) void k_tsp_pp2(
     const long long cand0 = blockIdx.x / npg;
     const int pg = blockIdx.x - (int)cand0 * npg;
     const int ngr = npg * G, gg = pg * G + g;  // pair groups in all, this wave's group
-    const int ndof = n * D;
-    double* s_V = smem;           // [n][4]
-    double* s_ctrl = s_V + ndof;  // [n][4]
+    const TspPpLds L = tsp_pp_layout(n, false);  // (sspp_lds.h)
+    double* s_V = smem;            // [n][4]
+    double* s_ctrl = s_V + L.n_V;  // [n][4]
     const long long nfx = a.ces ? (long long)*a.nfixed : 0;
     tsp_prologue(a, tsp_var(a), Minv, mean, sigma, vias_in, pg == 0 ? vias_out : nullptr, tid, NT, 1, cand0, 1, nfx,
                  s_V, s_ctrl);
@@ -3033,8 +2643,6 @@ __global__ __launch_bounds__(64 * G, 2) void k_tsp_pp2(
     finish_batch<NT>(bb, part, sync, best, (int)a.B, (int)cand0);
 }
 
-// ---------------------------------------------------------------- argmin over block results
-
 
 // TaskSpacePlanner batches up to this size take k_tsp_pp (one workgroup per candidate)
 constexpr int64_t kTspPpMaxBatch = 512;
@@ -3053,11 +2661,6 @@ inline size_t tsp_base_lds(int cpb, int n, int rep) {
     const int cpr = cpb * (rep > 1 ? rep : 1);
     return sizeof(double) * ((size_t)2 * cpr * n * 4 + 3 * (kBlock / 64) + (cpr > 4 ? cpr : 4)) +
            sizeof(int) * (size_t)((cpr + 1) & ~1);
-}
-
-inline int lanes_for(int items) {
-    int l = ((items + 63) / 64) * 64;
-    return std::min(std::max(l, 64), kBlock);
 }
 
 }  // namespace sspk
@@ -3238,7 +2841,6 @@ inline KScene kscene_job(const sspp_job* j, bool sampled) {
     return k;
 }
 
-// the split launch's second kernel: a persistent grid of the chip's resident capacity
 // whether a launch of nblk workgroups is one resident round (the split launch's waiting waves
 // need every producer resident); the occupancy query is cached per (kernel, LDS)
 inline bool c2f_one_round(const sspp_job* j, const void* fn, int nt, int lds, int nblk) {
@@ -3304,7 +2906,7 @@ hipError_t launch_census(const sspp_job* j, int M, unsigned long long seed, unsi
     SceneT T = scene_t_job(j, true);
     if (pairs) { T.pairs = pairs; T.visit = nullptr; }  // the asynchronous pre-pass's own copy of the sampled table
     const int r0 = std::min(P, j->n), r1 = std::max(r0, j->n - P);
-    const size_t lds = sizeof(double) * ((size_t)j->n * D + (size_t)(r1 - r0) * D + D);
+    const size_t lds = (size_t)census_layout(j->n, D, (r1 - r0) * D).bytes;
     const bool og = NM == 1 && sc.onegeom && sc.npairs > 0;
     if (sc.cylbox & kTableCapsule) {  // capsule pairs: the instantiations that carry their colliders
         if (og)
@@ -3364,72 +2966,67 @@ hipError_t entry_census(const sspp_job* j, int M, unsigned long long seed, unsig
 #endif
 }
 
+// The TaskSpacePlanner kernels' selection from the scene: f(og, cbm, up, def) is called once, with
+// std::integral_constants — og: one moving geom; cbm: 0 no cylinder-box or capsule pairs, 1 the exact
+// cylinder-box test, 2 its vertical / upright form; up: every box-box pair upright (never with
+// cbm 1); def: tsp_body's deferred-polygon form (0, 1, 2).
+template <class F>
+void tsp_dispatch(const KScene& sc, int def, F&& f) {
+    const bool og = sc.onegeom && sc.npairs > 0;
+    const int cbm = sc.cylbox ? (sc.cbup ? 2 : 1) : 0;
+    const bool up = sc.upright && cbm != 1;
+    auto pick_def = [&](auto ogc, auto cbc, auto upc) {
+        if (def == 1) f(ogc, cbc, upc, std::integral_constant<int, 1>{});
+        else if (def == 2) f(ogc, cbc, upc, std::integral_constant<int, 2>{});
+        else f(ogc, cbc, upc, std::integral_constant<int, 0>{});
+    };
+    auto pick_up = [&](auto ogc, auto cbc) {
+        if constexpr (decltype(cbc)::value != 1) {
+            if (up) return pick_def(ogc, cbc, std::true_type{});
+        }
+        pick_def(ogc, cbc, std::false_type{});
+    };
+    auto pick_cb = [&](auto ogc) {
+        if (cbm == 1) pick_up(ogc, std::integral_constant<int, 1>{});
+        else if (cbm == 2) pick_up(ogc, std::integral_constant<int, 2>{});
+        else pick_up(ogc, std::integral_constant<int, 0>{});
+    };
+    if (og) pick_cb(std::true_type{});
+    else pick_cb(std::false_type{});
+}
+// k_tsp's dynamic LDS: tsp_body's layout, with the DEF forms' records
+inline size_t tsp_lds(const TspK& k, const sspp_job* j, int def) {
+    const size_t base = tsp_base_lds(j->cpb, j->n, k.rep);
+    return def == 1 ? base + tsp_def_lds(k.sc.npairs) : (def == 2 ? base + tsp_def2_lds(k.sc.npairs) : base);
+}
+
 // TaskSpacePlanner evaluation (k_tsp), its own translation unit (SSPK_D = 0)
 template <int Unused>
 hipError_t entry_tsp(const TspK& k, const sspp_job* j, int nblk, const double* mean, const double* sigma,
                      const double* d_vias, double* d_vias_out, double* d_L, double* d_Cnf, double* d_Cwf,
                      double* d_cost, uint8_t* d_status, sspp_best* d_best, hipStream_t st, int pp) {
     const SceneT tt = scene_t(j->scene);
-    if (pp == 2) {  // k_tsp_pp2: k.npg 8-wave workgroups per candidate (nblk = B * npg)
-        const size_t lds = sizeof(double) * (size_t)2 * j->n * 4;
-#define SSPP_LAUNCH_TSPPP2(OG, CBV)                                                                       \
-        hipLaunchKernelGGL((k_tsp_pp2<1, OG, CBV, 8>), dim3(nblk), dim3(512), lds, st, k, tt, j->d_tab,   \
-                           j->d_span, j->d_Minv, mean, sigma, d_vias, d_vias_out, d_L, d_Cnf, d_Cwf, d_cost, \
-                           d_status, j->d_part, j->d_sync, d_best)
-        const bool og = k.sc.onegeom && k.sc.npairs > 0;
-        const int cbm = k.sc.cylbox ? (k.sc.cbup ? 2 : 1) : 0;
-        if (og && cbm == 1) SSPP_LAUNCH_TSPPP2(true, 1);
-        else if (og && cbm == 2) SSPP_LAUNCH_TSPPP2(true, 2);
-        else if (og) SSPP_LAUNCH_TSPPP2(true, 0);
-        else if (cbm == 1) SSPP_LAUNCH_TSPPP2(false, 1);
-        else if (cbm == 2) SSPP_LAUNCH_TSPPP2(false, 2);
-        else SSPP_LAUNCH_TSPPP2(false, 0);
-#undef SSPP_LAUNCH_TSPPP2
-        return hipGetLastError();
-    }
-    if (pp == 1) {  // k_tsp_pp: one 8-wave workgroup per candidate (cp <= 64, npairs <= 64)
-        const size_t lds = sizeof(double) * ((size_t)2 * j->n * 4 + 64 * 64) + 64 * 64;
-#define SSPP_LAUNCH_TSPPP(OG, CBV)                                                                       \
-        hipLaunchKernelGGL((k_tsp_pp<1, OG, CBV, 8>), dim3(nblk), dim3(512), lds, st, k, tt, j->d_tab,   \
-                           j->d_span, j->d_Minv, mean, sigma, d_vias, d_vias_out, d_L, d_Cnf, d_Cwf, d_cost, \
-                           d_status, j->d_part, j->d_sync, d_best)
-        const bool og = k.sc.onegeom && k.sc.npairs > 0;
-        const int cbm = k.sc.cylbox ? (k.sc.cbup ? 2 : 1) : 0;
-        if (og && cbm == 1) SSPP_LAUNCH_TSPPP(true, 1);
-        else if (og && cbm == 2) SSPP_LAUNCH_TSPPP(true, 2);
-        else if (og) SSPP_LAUNCH_TSPPP(true, 0);
-        else if (cbm == 1) SSPP_LAUNCH_TSPPP(false, 1);
-        else if (cbm == 2) SSPP_LAUNCH_TSPPP(false, 2);
-        else SSPP_LAUNCH_TSPPP(false, 0);
-#undef SSPP_LAUNCH_TSPPP
-        return hipGetLastError();
-    }
-#define SSPP_LAUNCH_TSP(OG, CBV, UPV, DEFV)                                                             \
-    hipLaunchKernelGGL((k_tsp<1, OG, CBV, UPV, DEFV>), dim3(nblk), dim3(kBlock), lds, st, k, tt, j->d_tab, \
-                       j->d_span, j->d_Minv, mean, sigma, d_vias, d_vias_out, d_L, d_Cnf, d_Cwf, d_cost, \
-                       d_status, j->d_part, j->d_sync, d_best)
-    const bool og = k.sc.onegeom && k.sc.npairs > 0;
-    const int cbm = k.sc.cylbox ? (k.sc.cbup ? 2 : 1) : 0;
-    const bool up = k.sc.upright && cbm != 1;
+    // pp == 2: k_tsp_pp2, k.npg 8-wave workgroups per candidate (nblk = B * npg);
+    // pp == 1: k_tsp_pp, one 8-wave workgroup per candidate (cp <= 64, npairs <= 64);
     // pp == 3: the deferred-polygon form (host-checked: one waypoint per lane, <= kDefPairs pairs);
     // pp == 4: the lane-local deferred polygons (one waypoint per lane, <= 64 pairs)
     const int def = pp == 3 ? 1 : (pp == 4 ? 2 : 0);
-    const size_t base = tsp_base_lds(j->cpb, j->n, k.rep);
-    const size_t lds = def == 1 ? base + tsp_def_lds(k.sc.npairs) : (def == 2 ? base + tsp_def2_lds(k.sc.npairs) : base);
-#define SSPP_LAUNCH_TSP_ALL(DEFV)                                                                         \
-    if (og && cbm == 1) SSPP_LAUNCH_TSP(true, 1, false, DEFV);                                            \
-    else if (og && cbm == 2) { if (up) SSPP_LAUNCH_TSP(true, 2, true, DEFV); else SSPP_LAUNCH_TSP(true, 2, false, DEFV); } \
-    else if (og && up) SSPP_LAUNCH_TSP(true, 0, true, DEFV);                                              \
-    else if (og) SSPP_LAUNCH_TSP(true, 0, false, DEFV);                                                   \
-    else if (cbm == 1) SSPP_LAUNCH_TSP(false, 1, false, DEFV);                                            \
-    else if (cbm == 2) { if (up) SSPP_LAUNCH_TSP(false, 2, true, DEFV); else SSPP_LAUNCH_TSP(false, 2, false, DEFV); } \
-    else if (up) SSPP_LAUNCH_TSP(false, 0, true, DEFV);                                                   \
-    else SSPP_LAUNCH_TSP(false, 0, false, DEFV);
-    if (def == 1) { SSPP_LAUNCH_TSP_ALL(1) }
-    else if (def == 2) { SSPP_LAUNCH_TSP_ALL(2) }
-    else { SSPP_LAUNCH_TSP_ALL(0) }
-#undef SSPP_LAUNCH_TSP_ALL
-#undef SSPP_LAUNCH_TSP
+    tsp_dispatch(k.sc, def, [&](auto og, auto cbm, auto up, auto defc) {
+        constexpr bool OG = decltype(og)::value, UP = decltype(up)::value;
+        constexpr int CBV = decltype(cbm)::value, DEFV = decltype(defc)::value;
+        if (pp == 2)
+            hipLaunchKernelGGL((k_tsp_pp2<1, OG, CBV, 8>), dim3(nblk), dim3(512), (size_t)tsp_pp_layout(j->n, false).bytes,
+                               st, k, tt, j->d_tab, j->d_span, j->d_Minv, mean, sigma, d_vias, d_vias_out, d_L, d_Cnf,
+                               d_Cwf, d_cost, d_status, j->d_part, j->d_sync, d_best);
+        else if (pp == 1)
+            hipLaunchKernelGGL((k_tsp_pp<1, OG, CBV, 8>), dim3(nblk), dim3(512), (size_t)tsp_pp_layout(j->n, true).bytes,
+                               st, k, tt, j->d_tab, j->d_span, j->d_Minv, mean, sigma, d_vias, d_vias_out, d_L, d_Cnf,
+                               d_Cwf, d_cost, d_status, j->d_part, j->d_sync, d_best);
+        else
+            hipLaunchKernelGGL((k_tsp<1, OG, CBV, UP, DEFV>), dim3(nblk), dim3(kBlock), tsp_lds(k, j, DEFV), st, k, tt,
+                               j->d_tab, j->d_span, j->d_Minv, mean, sigma, d_vias, d_vias_out, d_L, d_Cnf, d_Cwf,
+                               d_cost, d_status, j->d_part, j->d_sync, d_best);
+    });
     return hipGetLastError();
 }
 
@@ -3438,29 +3035,13 @@ template <int Unused>
 hipError_t entry_tsp_group(const TspK& k, const TspGoals& goals, const sspp_job* j, int nblk, hipStream_t st,
                            int mode) {
     const SceneT tt = scene_t(j->scene);
-#define SSPP_LAUNCH_TSPG(OG, CBV, UPV, DEFV)                                                            \
-    hipLaunchKernelGGL((k_tsp_group<1, OG, CBV, UPV, DEFV>), dim3(nblk), dim3(kBlock), lds, st, k, goals, tt, \
-                       j->d_tab, j->d_span, j->d_Minv)
-    const bool og = k.sc.onegeom && k.sc.npairs > 0;
-    const int cbm = k.sc.cylbox ? (k.sc.cbup ? 2 : 1) : 0;
-    const bool up = k.sc.upright && cbm != 1;
     const int def = mode == 3 ? 1 : (mode == 4 ? 2 : 0);
-    const size_t base = tsp_base_lds(j->cpb, j->n, k.rep);
-    const size_t lds = def == 1 ? base + tsp_def_lds(k.sc.npairs) : (def == 2 ? base + tsp_def2_lds(k.sc.npairs) : base);
-#define SSPP_LAUNCH_TSPG_ALL(DEFV)                                                                        \
-    if (og && cbm == 1) SSPP_LAUNCH_TSPG(true, 1, false, DEFV);                                           \
-    else if (og && cbm == 2) { if (up) SSPP_LAUNCH_TSPG(true, 2, true, DEFV); else SSPP_LAUNCH_TSPG(true, 2, false, DEFV); } \
-    else if (og && up) SSPP_LAUNCH_TSPG(true, 0, true, DEFV);                                             \
-    else if (og) SSPP_LAUNCH_TSPG(true, 0, false, DEFV);                                                  \
-    else if (cbm == 1) SSPP_LAUNCH_TSPG(false, 1, false, DEFV);                                           \
-    else if (cbm == 2) { if (up) SSPP_LAUNCH_TSPG(false, 2, true, DEFV); else SSPP_LAUNCH_TSPG(false, 2, false, DEFV); } \
-    else if (up) SSPP_LAUNCH_TSPG(false, 0, true, DEFV);                                                  \
-    else SSPP_LAUNCH_TSPG(false, 0, false, DEFV);
-    if (def == 1) { SSPP_LAUNCH_TSPG_ALL(1) }
-    else if (def == 2) { SSPP_LAUNCH_TSPG_ALL(2) }
-    else { SSPP_LAUNCH_TSPG_ALL(0) }
-#undef SSPP_LAUNCH_TSPG_ALL
-#undef SSPP_LAUNCH_TSPG
+    tsp_dispatch(k.sc, def, [&](auto og, auto cbm, auto up, auto defc) {
+        constexpr int DEFV = decltype(defc)::value;
+        hipLaunchKernelGGL((k_tsp_group<1, decltype(og)::value, decltype(cbm)::value, decltype(up)::value, DEFV>),
+                           dim3(nblk), dim3(kBlock), tsp_lds(k, j, DEFV), st, k, goals, tt, j->d_tab, j->d_span,
+                           j->d_Minv);
+    });
     return hipGetLastError();
 }
 

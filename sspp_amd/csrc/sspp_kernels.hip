@@ -1,6 +1,8 @@
 // sspp_kernels.hip — host side of the MI355X scorer: scenes, jobs, launches and the C ABI.
 //
-// The kernels are in sspp_kern.h; their instantiations are compiled per dof in sspp_inst.hip.
+// The kernels are in sspp_kern.h (their knobs, profiling hooks, LDS layouts and random numbers in
+// sspp_knobs.h, sspp_prof.h, sspp_lds.h, sspp_rng.h); their instantiations are compiled per dof in
+// sspp_inst.hip.
 #include "sspp_kern.h"
 
 #include <chrono>
@@ -788,11 +790,7 @@ static int set_job_tables(sspp_job* j, const double* init_ctrl, double sigma, co
 
 // k_sspp_c2f dynamic LDS bytes for cpb candidates of nrd own doubles each
 static size_t c2f_lds(const sspp_job* j, int cpb, int nrd) {
-    const int nm = j->nm < 1 ? 1 : j->nm;
-    const int rbox = std::max(6 * nm, lanes_for(j->W - 1) / 64 + 1);
-    return sizeof(double) * ((size_t)j->n * j->D + (size_t)cpb * (nrd + rbox) + j->D) +
-           sizeof(unsigned long long) * cpb + sizeof(int) * (3 * cpb + 1) +
-           sizeof(float) * ((size_t)j->n * j->D + (size_t)cpb * nrd);  // the FP32 copies
+    return (size_t)c2f_layout(j->n, j->D, cpb, nrd, j->nm < 1 ? 1 : j->nm, lanes_for(j->W - 1)).bytes;
 }
 
 // The FP32 filter's certified margin for a pair table (sspp_filter.h): FP32's error
@@ -849,7 +847,7 @@ static int prepass_start(sspp_job* j, const double* init_ctrl, double sigma, con
     Copies c{j->h_knots, std::vector<double>(init_ctrl, init_ctrl + (size_t)j->n * j->D),
              std::vector<double>(limits, limits + j->D), j->h_pairs, sigma, j->tables_gen};
     j->prepass_state.store(1, std::memory_order_relaxed);
-    j->prepass_thread = std::thread([j, sc, c = std::move(c), t0, M, nh]() mutable {
+    j->prepass_thread = std::thread([j, sc, c = std::move(c), t0, nh]() mutable {
         if (hipEventSynchronize(j->pre_ev) != hipSuccess) {
             j->prepass_state.store(3, std::memory_order_release);
             return;
@@ -1128,7 +1126,7 @@ static int run_sspp(sspp_job* j, const double* d_ctrl, int64_t first_id, int64_t
         c.linger = (unsigned long long)j->opt_linger_us * 100ull;  // the 100 MHz wall clock
         c.drop_orphans = j->opt_split_drop;
         // the last workgroup's per-step minimum bits, ids and counts reuse the LDS from offset 0
-        c.lds = std::max(c.lds, (int)(20 * kMaxSteps + 16));
+        c.lds = std::max(c.lds, c2f_split_layout().bytes);
     }
     SsppPtrs o{d_ctrl, d_ctrl_out, d_arc, d_feasible, d_best, q, &split_used};
     const int nb = nblk * steps;
