@@ -66,8 +66,8 @@ extern "C" {
 #define SSPP_E_INCOMPLETE (-7) /* a result record reports lost work (sspp_best::reserved != 0) */
 
 /* MuJoCo mjtGeom codes for the supported primitives.  Collision pairs: every pair of plane,
-   sphere, capsule, cylinder and box except cylinder-cylinder and capsule-cylinder (a scene that
-   needs one is refused with SSPP_E_UNSUPPORTED); meshes are parsed but never collide.  A capsule
+   sphere, capsule, cylinder and box except capsule-cylinder (a scene that needs one is refused
+   with SSPP_E_UNSUPPORTED); meshes are parsed but never collide.  A capsule
    is size[0] = radius, size[1] = half-length of its cylindrical part, along the frame's z axis. */
 #define SSPP_GEOM_PLANE 0
 #define SSPP_GEOM_SPHERE 2
@@ -265,6 +265,8 @@ void sspp_job_free(sspp_job* job);
 #define SSPP_OPT_SPLIT_LOST 23  /* get (synchronous): survivors lost so far (0 unless DROP)     */
 #define SSPP_OPT_CAPSULE 24     /* get: the sampled-candidate table has capsule pairs (the kernels
                                    that carry the capsule colliders run; mirrors SSPP_OPT_CYLBOX)  */
+#define SSPP_OPT_CYLCYL 25      /* get: the sampled-candidate table has cylinder-cylinder pairs
+                                   (mirrors SSPP_OPT_CYLBOX / SSPP_OPT_CAPSULE)                    */
 #define SSPP_OPT_TSP_REP 19     /* TaskSpacePlanner k_tsp form 3: sub-batches of candidates
                                    per workgroup (one prologue for all of them), 1..16, -1 by batch
                                    size; get: the last k_tsp launch's                            */

@@ -173,6 +173,7 @@ OPT_CYLBOX, OPT_F32, OPT_LAST_F32, OPT_CREATE_US, OPT_PREPASS_STATE = 12, 13, 14
 OPT_SPLIT, OPT_LAST_SPLIT, OPT_TSP_REP = 17, 18, 19
 OPT_SPLIT_LINGER_US, OPT_SPLIT_DROP, OPT_SPLIT_HANDOFFS, OPT_SPLIT_LOST = 20, 21, 22, 23
 OPT_CAPSULE = 24
+OPT_CYLCYL = 25
 OPT_CES_FUSED = 101
 
 

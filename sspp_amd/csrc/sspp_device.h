@@ -1254,13 +1254,219 @@ SSPP_HD int col_capsule_box(const double* cp, const double* cm, const double* sz
     return nc;
 }
 
+// ---------------------------------------------------------------- cylinder-cylinder, exact
+// The signed distance is the maximum over unit n of n.(c2 - c1) - h1(n) - h2(n) with the support
+// functions h_i(n) = H_i |a_i.n| + R_i sqrt(1 - (a_i.n)^2); every direction is a lower bound, and
+// the maximum sits at the normal of the closest feature pair:
+//   (a) a cap of either cylinder: a_1, a_2          (b) lateral vs lateral: a_1 x a_2
+//   (c) a lateral surface vs a rim circle of the other cylinder: the common normals of the axis
+//       line and the circle
+//   (d) rim circle vs rim circle: the common normals of two circles.
+// (c) and (d) are the zeros of one periodic function of the angle on a rim (cc_resid): the
+// tangential component of the offset from the rim point to the critical point of the other
+// feature that belongs to it.  They are bracketed by kCcSamples samples and bisected.
+// Everything runs in cylinder 1's frame (axis z, centre 0).
+struct CylCyl {
+    double T[3];  // centre of cylinder 2
+    double b[3];  // axis of cylinder 2
+    double R1, H1, R2, H2;
+};
+SSPP_HD CylCyl make_cylcyl(const double* p1, const double* m1, const double* s1, const double* p2,
+                           const double* m2, const double* s2) {
+    CylCyl c;
+    const double d[3] = {p2[0] - p1[0], p2[1] - p1[1], p2[2] - p1[2]};
+    double a2[3], ax[3];
+    col3(m2, 2, a2);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { col3(m1, k, ax); c.T[k] = dot3(ax, d); c.b[k] = dot3(ax, a2); }
+    c.R1 = s1[0]; c.H1 = s1[1]; c.R2 = s2[0]; c.H2 = s2[1];
+    return c;
+}
+// true iff the separation along L (any length) is >= thr.  |a x L| by the cross product: the
+// difference |L|^2 - (a.L)^2 loses half the digits when L is along a, which is a cap contact.
+SSPP_HD bool cc_sep(const CylCyl& c, const double* L, double thr) {
+    const double len2 = dot3(L, L);
+    if (!(len2 > 1e-30)) return false;
+    const double x[3] = {c.b[1] * L[2] - c.b[2] * L[1], c.b[2] * L[0] - c.b[0] * L[2], c.b[0] * L[1] - c.b[1] * L[0]};
+    const double r1 = fma(c.H1, fabs(L[2]), c.R1 * sqrt(fma(L[1], L[1], L[0] * L[0])));
+    const double r2 = fma(c.H2, fabs(dot3(c.b, L)), c.R2 * sqrt(dot3(x, x)));
+    const double num = fabs(dot3(c.T, L)) - (r1 + r2);
+    return thr == 0.0 ? num >= 0.0 : num >= thr * sqrt(len2);
+}
+// families (a), (b)
+SSPP_HD bool cc_base_sep(const CylCyl& c, double thr) {
+    const double z[3] = {0.0, 0.0, 1.0};
+    if (cc_sep(c, z, thr)) return true;
+    if (cc_sep(c, c.b, thr)) return true;
+    const double L[3] = {-c.b[1], c.b[0], 0.0};
+    if (dot3(L, L) < 1e-12) return false;  // parallel axes: family (c)
+    return cc_sep(c, L, thr);
+}
+// Nearest point y of the cylinder (centre o, unit axis a, radius R, half height H) to x, and
+// whether x lies strictly inside it.
+SSPP_HD bool cc_proj(const double* o, const double* a, double R, double H, const double* x, double* y) {
+    const double w[3] = {x[0] - o[0], x[1] - o[1], x[2] - o[2]};
+    const double z = dot3(a, w);
+    const double r[3] = {w[0] - z * a[0], w[1] - z * a[1], w[2] - z * a[2]};
+    const double rr = dot3(r, r);
+    const bool in = rr < R * R && z < H && z > -H;
+    const double zc = z > H ? H : (z < -H ? -H : z);
+    const double f = rr > R * R ? R / sqrt(rr) : 1.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) y[i] = o[i] + fma(zc, a[i], f * r[i]);
+    return in;
+}
+// Alternating nearest points x (cylinder 1, shrunk by dl) and y (cylinder 2).  1: overlap proven —
+// x strictly inside cylinder 2 or y strictly inside the shrunk cylinder 1 (signed distance <
+// -dl: (A (-) ball) - B lies in (A - B) (-) ball), or, for dl = 0 and thr > 0, |x - y| < thr.
+// -1: the last offset x - y separates by >= thr.  0: undecided.
+SSPP_HD int cc_witness(const CylCyl& c, double dl, double thr) {
+    const double o1[3] = {0.0, 0.0, 0.0}, z[3] = {0.0, 0.0, 1.0};
+    double x[3], y[3] = {c.T[0], c.T[1], c.T[2]}, d[3] = {0.0, 0.0, 0.0};
+    if (!(c.R1 > dl && c.H1 > dl)) return 0;
+#pragma unroll 1
+    for (int it = 0; it < 4; ++it) {
+        if (cc_proj(o1, z, c.R1 - dl, c.H1 - dl, y, x)) return 1;
+        if (cc_proj(c.T, c.b, c.R2, c.H2, x, y)) return 1;
+        d[0] = x[0] - y[0]; d[1] = x[1] - y[1]; d[2] = x[2] - y[2];
+        if (dl == 0.0 && thr > 0.0 && dot3(d, d) < thr * thr) return 1;
+    }
+    return (dl == 0.0 && cc_sep(c, d, thr)) ? -1 : 0;
+}
+// The roles swapped: cylinder 2's frame (x axis along a_1 x a_2, or any normal of the axis when
+// the two are parallel), so that the rim scans below run on either cylinder.
+SSPP_HD CylCyl cc_swap(const CylCyl& c) {
+    double e[3] = {-c.b[1], c.b[0], 0.0};
+    if (dot3(e, e) < 1e-12) { e[0] = 1.0; e[1] = 0.0; }
+    const double eb = dot3(e, c.b);
+    double u[3] = {e[0] - eb * c.b[0], e[1] - eb * c.b[1], e[2] - eb * c.b[2]};
+    const double iu = 1.0 / sqrt(dot3(u, u));
+    u[0] *= iu; u[1] *= iu; u[2] *= iu;
+    const double v[3] = {c.b[1] * u[2] - c.b[2] * u[1], c.b[2] * u[0] - c.b[0] * u[2], c.b[0] * u[1] - c.b[1] * u[0]};
+    CylCyl s;
+    s.T[0] = -dot3(u, c.T); s.T[1] = -dot3(v, c.T); s.T[2] = -dot3(c.b, c.T);
+    s.b[0] = u[2]; s.b[1] = v[2]; s.b[2] = c.b[2];
+    s.R1 = c.R2; s.H1 = c.H2; s.R2 = c.R1; s.H2 = c.H1;
+    return s;
+}
+// The rim point p = (R1 cs, R1 sn, hs) of cylinder 1 against a feature of cylinder 2 — its axis
+// line (line) or its rim circle at height ho, the circle's nearest (sg = 1) or farthest (sg = -1)
+// point to p: L = the offset from that feature's point to p; returns L's component along the
+// rim's tangent at p (zero at a common normal).
+SSPP_HD double cc_resid(const CylCyl& c, double cs, double sn, double hs, bool line, double ho, double sg,
+                        double* L) {
+    const double w[3] = {fma(c.R1, cs, -fma(ho, c.b[0], c.T[0])), fma(c.R1, sn, -fma(ho, c.b[1], c.T[1])),
+                         hs - fma(ho, c.b[2], c.T[2])};
+    const double wb = dot3(w, c.b);
+    const double wp[3] = {w[0] - wb * c.b[0], w[1] - wb * c.b[1], w[2] - wb * c.b[2]};
+    if (line) {
+        L[0] = wp[0]; L[1] = wp[1]; L[2] = wp[2];
+    } else {
+        // (where p crosses the other circle's axis, lp -> 0, the residual jumps: a bracket around
+        // the jump bisects to a direction that is no common normal, only one more lower bound)
+        const double lp = sqrt(dot3(wp, wp));
+        const double f = lp > 1e-300 ? 1.0 - sg * c.R2 / lp : 1.0;
+        L[0] = fma(f, wp[0], wb * c.b[0]); L[1] = fma(f, wp[1], wb * c.b[1]); L[2] = fma(f, wp[2], wb * c.b[2]);
+    }
+    return fma(cs, L[1], -sn * L[0]);
+}
+// One scan of a rim of cylinder 1: true iff a common normal found separates by >= thr.
+constexpr int kCcSamples = 24;
+SSPP_HD bool cc_scan(const CylCyl& c, double hs, bool line, double ho, double sg, double thr) {
+    const double C = 0.96592582628906829, S = 0.25881904510252076;  // cos, sin of 2 pi / 24
+    double L[3];
+    double c0 = 1.0, s0 = 0.0, r0 = cc_resid(c, c0, s0, hs, line, ho, sg, L);
+#pragma unroll 1
+    for (int k = 0; k < kCcSamples; ++k) {
+        double c1 = fma(c0, C, -s0 * S), s1 = fma(s0, C, c0 * S);
+        if (k == kCcSamples - 1) { c1 = 1.0; s1 = 0.0; }
+        const double r1 = cc_resid(c, c1, s1, hs, line, ho, sg, L);
+        if ((r0 <= 0.0 && r1 > 0.0) || (r0 >= 0.0 && r1 < 0.0)) {
+            double ca = c0, sa = s0, cb = c1, sb = s1;
+            const bool up = r1 > 0.0;  // the residual rises across the bracket
+#pragma unroll 1
+            for (int it = 0; it < 36; ++it) {
+                const double mx = ca + cb, my = sa + sb;
+                const double im = 1.0 / sqrt(fma(my, my, mx * mx));
+                const double cm = mx * im, sm = my * im;
+                const double rm = cc_resid(c, cm, sm, hs, line, ho, sg, L);
+                if ((rm > 0.0) == up) { cb = cm; sb = sm; } else { ca = cm; sa = sm; }
+            }
+            cc_resid(c, ca, sa, hs, line, ho, sg, L);
+            if (cc_sep(c, L, thr)) return true;
+        }
+        c0 = c1; s0 = s1; r0 = r1;
+    }
+    return false;
+}
+// families (c) and (d); all_roots adds (d)'s far-point branch (a penetration depth's normal can
+// be one)
+SSPP_HD bool cc_ext_sep(const CylCyl& c, double thr, bool all_roots) {
+    const CylCyl s = cc_swap(c);
+#pragma unroll 1
+    for (int r = 0; r < 2; ++r) {
+        const double h1 = r ? c.H1 : -c.H1, h2 = r ? c.H2 : -c.H2;
+        if (cc_scan(c, h1, true, 0.0, 1.0, thr)) return true;   // rim of 1 vs lateral surface of 2
+        if (cc_scan(s, h2, true, 0.0, 1.0, thr)) return true;   // rim of 2 vs lateral surface of 1
+#pragma unroll 1
+        for (int q = 0; q < 2; ++q) {
+            const double ho = q ? c.H2 : -c.H2;
+            if (cc_scan(c, h1, false, ho, 1.0, thr)) return true;
+            if (all_roots && cc_scan(c, h1, false, ho, -1.0, thr)) return true;
+        }
+    }
+    return false;
+}
+// Past the axes (a), (b), from cylinder 1's frame: 10 doubles and the threshold (the argument
+// registers of a call) — the witnesses, then the search.  `stage` (host checks only) receives
+// what decided: 1 a witness, 2 the witness's offset, 3 the search.
+SSPP_HD bool cc_rest_overlap(double T0, double T1, double T2, double b0, double b1, double b2, double R1,
+                             double H1, double R2, double H2, double thr, int* stage = nullptr) {
+    CylCyl c;
+    c.T[0] = T0; c.T[1] = T1; c.T[2] = T2;
+    c.b[0] = b0; c.b[1] = b1; c.b[2] = b2;
+    c.R1 = R1; c.H1 = H1; c.R2 = R2; c.H2 = H2;
+    const int w = cc_witness(c, 0.0, thr);
+    if (stage) *stage = w < 0 ? 2 : 1;
+    if (w < 0) return false;
+    if (thr >= 0.0 ? w > 0 : (cc_witness(c, -thr, thr) > 0 || cc_witness(cc_swap(c), -thr, thr) > 0)) return true;
+    if (stage) *stage = 3;
+    return !cc_ext_sep(c, thr, thr < 0.0);
+}
+// Out of line, for kernels at their register budget (k_tsp): only the three axes run inline.
+__host__ __device__ inline __attribute__((noinline)) bool cc_rest_overlap_call(
+    double T0, double T1, double T2, double b0, double b1, double b2, double R1, double H1, double R2,
+    double H2, double thr) {
+    return cc_rest_overlap(T0, T1, T2, b0, b1, b2, R1, H1, R2, H2, thr);
+}
+// Both axes vertical (cyl_vertical): two prisms along z, the analogue of cb_upright_sd.
+SSPP_HD double cc_vertical_sd(const double* p1, const double* s1, const double* p2, const double* s2) {
+    const double d0 = p2[0] - p1[0], d1 = p2[1] - p1[1], d2 = p2[2] - p1[2];
+    const double dr = sqrt(fma(d1, d1, d0 * d0)) - (s1[0] + s2[0]);
+    const double dz = fabs(d2) - (s1[1] + s2[1]);
+    if (dr > 0.0 && dz > 0.0) return sqrt(fma(dr, dr, dz * dz));
+    return dr > dz ? dr : dz;
+}
+// cylinder vs cylinder: signed distance < thr (thr = margin >= 0, or kDeep).  The axes (a), (b)
+// separate most pairs (stage 0); the rest (OUTLINE: as a call) is cc_rest_overlap.
+template <bool OUTLINE>
+SSPP_HD bool cyl_cyl_overlap(const double* p1, const double* m1, const double* s1, const double* p2,
+                             const double* m2, const double* s2, double thr, int* stage = nullptr) {
+    const CylCyl c = make_cylcyl(p1, m1, s1, p2, m2, s2);
+    if (stage) *stage = 0;
+    if (cc_base_sep(c, thr)) return false;
+    if (OUTLINE)
+        return cc_rest_overlap_call(c.T[0], c.T[1], c.T[2], c.b[0], c.b[1], c.b[2], c.R1, c.H1, c.R2, c.H2, thr);
+    return cc_rest_overlap(c.T[0], c.T[1], c.T[2], c.b[0], c.b[1], c.b[2], c.R1, c.H1, c.R2, c.H2, thr, stage);
+}
+
 // Supported narrowphase pair? (types ordered t1 <= t2)
 SSPP_HD bool pair_supported(int t1, int t2) {
     if (t1 > t2) { int t = t1; t1 = t2; t2 = t; }
     if (t1 == 0) return t2 == 0 || t2 == 2 || t2 == 3 || t2 == 5 || t2 == 6;
     if (t1 == 2) return t2 == 2 || t2 == 3 || t2 == 5 || t2 == 6;
     if (t1 == 3) return t2 == 3 || t2 == 6;  // capsule-cylinder: not built
-    return (t1 == 5 && t2 == 6) || (t1 == 6 && t2 == 6);
+    return (t1 == 5 && (t2 == 5 || t2 == 6)) || (t1 == 6 && t2 == 6);
 }
 SSPP_HD bool pair_has_capsule(int t1, int t2) { return t1 == 3 || t2 == 3; }
 
@@ -1281,8 +1487,11 @@ SSPP_HD bool pair_has_capsule(int t1, int t2) { return t1 == 3 || t2 == 3; }
 // CAPDEFER (feasibility only): a pair with a capsule in it returns -1, undecided, like a
 // deferred cylinder-box pair, and the caller settles it later (k_sspp_c2f's pair loops carry no
 // capsule code; c2f_cb_exact does).
+// CC, cylinder-cylinder pairs: 0 none in the table (code compiled out), 1 the exact test (two
+// vertical cylinders take cc_vertical_sd), 2 every such pair is vertical (host-checked):
+// cc_vertical_sd only, 3 (feasibility only) returns -1, undecided, like CAPDEFER.
 template <bool NEED_DEEP, int CB = 1, bool OUTLINE = false, bool DEFER = false, bool UP = false, bool CAP = true,
-          bool CAPDEFER = false>
+          bool CAPDEFER = false, int CC = 1>
 SSPP_HD int collide(int t1, const double* p1, const double* m1, const double* s1, int t2,
                     const double* p2, const double* m2, const double* s2, double margin, int* nd) {
     *nd = 0;
@@ -1305,6 +1514,26 @@ SSPP_HD int collide(int t1, const double* p1, const double* m1, const double* s1
         if (t2 == 3) return col_capsule_capsule(p1, m1, s1, p2, m2, s2, margin, nd);
         if (t2 == 6) return col_capsule_box(p1, m1, s1, p2, m2, s2, margin, nd);
         return 0;
+    }
+    if (CC != 0 && t1 == 5 && t2 == 5) {  // cylinder-cylinder: the cylinder-box rule
+        if (CC == 3 && !NEED_DEEP) return -1;
+        if (CC == 2 || (cyl_vertical(m1) && cyl_vertical(m2))) {
+            const double sd = cc_vertical_sd(p1, s1, p2, s2);
+            if (NEED_DEEP) {
+                const int d = (margin >= deep_thr()) ? (sd < deep_thr()) : (sd < margin && sd < deep_thr());
+                *nd = d;
+                return d;
+            }
+            return sd < margin ? 1 : 0;
+        }
+        if (NEED_DEEP) {
+            int d = (margin >= deep_thr()) ? (int)cyl_cyl_overlap<OUTLINE>(p1, m1, s1, p2, m2, s2, deep_thr())
+                                      : (int)(cyl_cyl_overlap<OUTLINE>(p1, m1, s1, p2, m2, s2, margin) &&
+                                              cyl_cyl_overlap<OUTLINE>(p1, m1, s1, p2, m2, s2, deep_thr()));
+            *nd = d;
+            return d;
+        }
+        return cyl_cyl_overlap<OUTLINE>(p1, m1, s1, p2, m2, s2, margin) ? 1 : 0;
     }
     if (t1 == 5) {  // cylinder-box: exact signed distance test, one contact (MuJoCo's convex collider)
         if (!CB) return 0;

@@ -49,10 +49,10 @@ namespace sspk {
 constexpr int kMaxMovers = 2;
 
 // what a pair contributes to its table's kernel selection (KScene::cylbox, sspp_job::cb_*)
-constexpr int kTableCylBox = 1, kTableCapsule = 2;
+constexpr int kTableCylBox = 1, kTableCapsule = 2, kTableCylCyl = 4;
 __host__ __device__ inline int table_bits(int tg, int to) {
     return (((tg == 5 && to == 6) || (tg == 6 && to == 5)) ? kTableCylBox : 0) |
-           (sspd::pair_has_capsule(tg, to) ? kTableCapsule : 0);
+           (sspd::pair_has_capsule(tg, to) ? kTableCapsule : 0) | ((tg == 5 && to == 5) ? kTableCylCyl : 0);
 }
 
 struct KScene {
@@ -61,9 +61,10 @@ struct KScene {
     int static_block;   // sspp: env-env contacts counted and present -> nothing feasible
     double static_cost; // tsp: Collision.h cost of env-env contacts, added per waypoint
     int cylbox;         // table_bits of the moving pairs: non-zero selects the kernels that carry the
-                        // cylinder-box and capsule code (CBX / CB = 1)
+                        // cylinder-box, capsule and cylinder-cylinder code (CBX / CB = 1, 3)
     int upright;        // tsp: every box-box pair is upright for a yaw-only mover (k_tsp<..., UP>)
-    int cbup;           // tsp: every cylinder-box pair is vertical / upright (collide<..., CB = 2>)
+    int cbup;           // tsp: every cylinder-box and cylinder-cylinder pair is vertical / upright
+                        // (collide<..., CB = 2>; with a cylinder-cylinder pair CB = 3)
 };
 
 // Scene tables are passed as separate __restrict__ kernel arguments: the pair loop is
@@ -386,6 +387,8 @@ __device__ __forceinline__ void geom_rot_t(const double* R, const DGeom& G, doub
 // REC 4 (k_tsp<..., DEF 2>): the records of REC 3 without the terms — the lane itself sums its
 // records after the pair loop (tsp_lane_sum), recomputing each term from the recorded pose.
 constexpr int kBbPend = 16;
+// CB = 3: CB = 2 plus the vertical closed form of cylinder-cylinder pairs (collide<..., CC = 2>);
+// CB = 1 carries their exact test beside the capsule colliders.
 template <int D, int NM, int MODE, bool DEEP, bool ONEGEOM, int CB = 1, int REC = 0, bool UP = false>
 __device__ int point_collide(const double* q, const KScene& sc, const SceneT& T,
                              unsigned long long mask, double* cost, int* stop = nullptr,
@@ -489,9 +492,9 @@ __device__ int point_collide(const double* q, const KScene& sc, const SceneT& T,
                                            : box_box_deep_class(op, om, pr.osize, gp, gmat, G.size));
                 nd = c < 0 ? 0 : (c == 6 ? 1 : kBbPend + c);
             } else if (gfirst) {
-                nc = collide<DEEP, CB, DEEP, false, UP, CB == 1>(G.type, gp, gmat, G.size, pr.otype, op, om, pr.osize, pr.margin, &nd);
+                nc = collide<DEEP, CB == 3 ? 2 : CB, DEEP, false, UP, CB == 1, false, CB == 1 ? 1 : (CB == 3 ? 2 : 0)>(G.type, gp, gmat, G.size, pr.otype, op, om, pr.osize, pr.margin, &nd);
             } else {
-                nc = collide<DEEP, CB, DEEP, false, UP, CB == 1>(pr.otype, op, om, pr.osize, G.type, gp, gmat, G.size, pr.margin, &nd);
+                nc = collide<DEEP, CB == 3 ? 2 : CB, DEEP, false, UP, CB == 1, false, CB == 1 ? 1 : (CB == 3 ? 2 : 0)>(pr.otype, op, om, pr.osize, G.type, gp, gmat, G.size, pr.margin, &nd);
             }
         }
         if (DEEP) TSP_STAT(5, nd > 0);
@@ -873,11 +876,13 @@ __device__ __forceinline__ void eval_split_g(const double* sm, int mine, int fix
 // CAP: 0 no capsule pairs in the table (their colliders compiled out), 1 a capsule pair past the
 // bounding-sphere test is left undecided like a cylinder-box pair (k_sspp_c2f: settled by
 // c2f_cb_exact, so the pair loops of the cylinder-box kernels are what they were), 2 tested here
-// (k_sspp_census).
+// (k_sspp_census).  Cylinder-cylinder pairs ride with the capsule pairs: none, left undecided,
+// tested here.
 template <int D, int NM, bool ONEGEOM, int CAP = 0>
 __device__ __forceinline__ bool scan_pairs(const double* q, bool live, unsigned long long mymask,
                                            unsigned long long umask, unsigned long long gbits,
                                            int* flag, const KScene& sc, const SceneT& T, bool& dfr) {
+    constexpr int kCC = CAP == 0 ? 0 : (CAP == 1 ? 3 : 1);  // collide's CC
     const cgeom_t geoms = (cgeom_t)T.geoms;
     const cpair_t pairs = (cpair_t)T.pairs;
     double mp[NM][3], mR[NM][9];
@@ -933,8 +938,8 @@ __device__ __forceinline__ bool scan_pairs(const double* q, bool live, unsigned 
                 }
                 int nd = 0;
                 const bool gfirst = (G.type < pr.otype) || (G.type == pr.otype && G.orig < pr.oorig);
-                if (gfirst) nc = collide<false, true, false, true, false, CAP != 0, CAP == 1>(G.type, gp, gmat, G.size, pr.otype, op, om, pr.osize, pr.margin, &nd);
-                else nc = collide<false, true, false, true, false, CAP != 0, CAP == 1>(pr.otype, op, om, pr.osize, G.type, gp, gmat, G.size, pr.margin, &nd);
+                if (gfirst) nc = collide<false, true, false, true, false, CAP != 0, CAP == 1, kCC>(G.type, gp, gmat, G.size, pr.otype, op, om, pr.osize, pr.margin, &nd);
+                else nc = collide<false, true, false, true, false, CAP != 0, CAP == 1, kCC>(pr.otype, op, om, pr.osize, G.type, gp, gmat, G.size, pr.margin, &nd);
                 if (nc < 0) { dfr = true; nc = 0; }
             }
         }
@@ -1127,7 +1132,8 @@ __device__ __forceinline__ void wave_compact(int tid, bool keep, int value, int*
 // job's own distribution touch the scene: one workgroup per census candidate draws it
 // (sampleWithNoise, the job's sigma / limits, an independent seed) and tests every collision
 // waypoint u = i / W, one per lane, against the sampled-candidate pair table (scan_pairs; a
-// cylinder-box pair left undecided counts as no contact: the census only steers the order).
+// cylinder-box pair left undecided counts as no contact: the census only steers the order; the
+// CAP variant tests capsule and cylinder-cylinder pairs here).
 // Output: hit bits [M][ceil((W+1) / 64)], bit i = contact at waypoint i.
 constexpr int kCensusThreads = 256;
 template <int D, int NM, int P, bool ONEGEOM, bool CAP = false>
@@ -1161,9 +1167,10 @@ __global__ __launch_bounds__(kCensusThreads) void k_sspp_census(
     }
 }
 
-// The exact cylinder-box test (witnesses + candidate search, sspd::cyl_box_overlap) and the
-// capsule colliders of one waypoint of one candidate over its cylinder-box and capsule pairs
-// (the pairs the scans leave undecided).  Out of line: it runs only for the
+// The exact cylinder-box and cylinder-cylinder tests (witnesses + candidate search,
+// sspd::cyl_box_overlap / cyl_cyl_overlap) and the capsule colliders of one waypoint of one
+// candidate over its cylinder-box, cylinder-cylinder and capsule pairs (the pairs the scans
+// leave undecided).  Out of line: it runs only for the
 // candidates the scans left undecided, and its registers stay out of the kernel's pair loops.
 template <int D, int NM, int P>
 __device__ SSPP_CB_INLINE bool c2f_cb_exact(const double* sm, int mine, int fix, int r0, int r1,
@@ -1179,7 +1186,7 @@ __device__ SSPP_CB_INLINE bool c2f_cb_exact(const double* sm, int mine, int fix,
         if (k < 64 && !((mask >> k) & 1ull)) continue;
         const DPair pr = load_pair(pairs + k);
         const DGeom G = load_geom(geoms + pr.gm);
-        if (table_bits(G.type, pr.otype) == 0) continue;  // cylinder-box and capsule pairs only
+        if (table_bits(G.type, pr.otype) == 0) continue;  // cylinder-box, capsule, cylinder-cylinder pairs only
         const bool second = NM > 1 && G.mover == 1;
         double gp[3], gmat[9], op_[3], om_[9];
         geom_pose(second ? mp[NM - 1] : mp[0], second ? mR[NM - 1] : mR[0], G, gp, gmat);
@@ -1198,8 +1205,8 @@ __device__ SSPP_CB_INLINE bool c2f_cb_exact(const double* sm, int mine, int fix,
         if (!pair_near(pr, G.rbound, gp, op, om)) continue;
         int nd = 0;
         const bool gfirst = (G.type < pr.otype) || (G.type == pr.otype && G.orig < pr.oorig);
-        const int nc = gfirst ? collide<false, 1, false, false, false, true>(G.type, gp, gmat, G.size, pr.otype, op, om, pr.osize, pr.margin, &nd)
-                              : collide<false, 1, false, false, false, true>(pr.otype, op, om, pr.osize, G.type, gp, gmat, G.size, pr.margin, &nd);
+        const int nc = gfirst ? collide<false, 1, false, false, false, true, false, 1>(G.type, gp, gmat, G.size, pr.otype, op, om, pr.osize, pr.margin, &nd)
+                              : collide<false, 1, false, false, false, true, false, 1>(pr.otype, op, om, pr.osize, G.type, gp, gmat, G.size, pr.margin, &nd);
         if (nc > 0) return true;
     }
     return false;
@@ -1331,8 +1338,9 @@ __device__ __forceinline__ void surv_finish(const SsppC2F& a, const SceneT& TT, 
     __syncthreads();  // the next survivor may overwrite the rows and the flags
 }
 
-// CBX: the pair table has cylinder-box or capsule pairs, so the kernel carries the settle step (its
-// out-of-line exact test costs the whole kernel registers: 96 -> 128 VGPRs and scratch)
+// CBX: the pair table has cylinder-box, cylinder-cylinder or capsule pairs, so the kernel carries
+// the settle step (its out-of-line exact test costs the whole kernel registers: 96 -> 128 VGPRs
+// and scratch)
 // SPLIT: the split launch's instance (single-geom movers without cylinder-box pairs): phase 1,
 // then the survivor queue; the in-workgroup phases 2-4 are unreachable there and compiled out, so
 // the queue costs the unsplit instances no registers
@@ -2801,6 +2809,8 @@ inline KScene kscene(const sspp_scene* s, bool tsp, bool generic = false) {
             k.cbup &= (!g.relrot || sspd::cyl_vertical(g.mat)) && sspd::upright3(p.omat);
         if (tg == 6 && p.otype == 5)
             k.cbup &= (!g.relrot || sspd::upright3(g.mat)) && sspd::cyl_vertical(p.omat);
+        if (tg == 5 && p.otype == 5)
+            k.cbup &= (!g.relrot || sspd::cyl_vertical(g.mat)) && sspd::cyl_vertical(p.omat);
     }
     return k;
 }
@@ -2908,7 +2918,7 @@ hipError_t launch_census(const sspp_job* j, int M, unsigned long long seed, unsi
     const int r0 = std::min(P, j->n), r1 = std::max(r0, j->n - P);
     const size_t lds = (size_t)census_layout(j->n, D, (r1 - r0) * D).bytes;
     const bool og = NM == 1 && sc.onegeom && sc.npairs > 0;
-    if (sc.cylbox & kTableCapsule) {  // capsule pairs: the instantiations that carry their colliders
+    if (sc.cylbox & (kTableCapsule | kTableCylCyl)) {  // the instantiations that carry those pairs' colliders
         if (og)
             hipLaunchKernelGGL((k_sspp_census<D, 1, P, true, true>), dim3(M), dim3(kCensusThreads), lds, st, sc, T,
                                j->n, j->W, j->sampler, j->sigma, seed, j->d_tab, j->d_span, j->d_init, j->d_limits,
@@ -2967,13 +2977,18 @@ hipError_t entry_census(const sspp_job* j, int M, unsigned long long seed, unsig
 }
 
 // The TaskSpacePlanner kernels' selection from the scene: f(og, cbm, up, def) is called once, with
-// std::integral_constants — og: one moving geom; cbm: 0 no cylinder-box or capsule pairs, 1 the exact
-// cylinder-box test, 2 its vertical / upright form; up: every box-box pair upright (never with
-// cbm 1); def: tsp_body's deferred-polygon form (0, 1, 2).
+// std::integral_constants — og: one moving geom; cbm: tsp_cbm's value; up: every box-box pair
+// upright (never with cbm 1); def: tsp_body's deferred-polygon form (0, 1, 2).
+// cbm: 0 no cylinder-box, cylinder-cylinder or capsule pairs, 1 the exact cylinder-box and
+// cylinder-cylinder tests, 2 the vertical / upright form of cylinder-box pairs, 3 that and the
+// vertical form of cylinder-cylinder pairs
+inline int tsp_cbm(const KScene& sc) {
+    return sc.cylbox ? (sc.cbup ? ((sc.cylbox & kTableCylCyl) ? 3 : 2) : 1) : 0;
+}
 template <class F>
 void tsp_dispatch(const KScene& sc, int def, F&& f) {
     const bool og = sc.onegeom && sc.npairs > 0;
-    const int cbm = sc.cylbox ? (sc.cbup ? 2 : 1) : 0;
+    const int cbm = tsp_cbm(sc);
     const bool up = sc.upright && cbm != 1;
     auto pick_def = [&](auto ogc, auto cbc, auto upc) {
         if (def == 1) f(ogc, cbc, upc, std::integral_constant<int, 1>{});
@@ -2989,6 +3004,7 @@ void tsp_dispatch(const KScene& sc, int def, F&& f) {
     auto pick_cb = [&](auto ogc) {
         if (cbm == 1) pick_up(ogc, std::integral_constant<int, 1>{});
         else if (cbm == 2) pick_up(ogc, std::integral_constant<int, 2>{});
+        else if (cbm == 3) pick_up(ogc, std::integral_constant<int, 3>{});
         else pick_up(ogc, std::integral_constant<int, 0>{});
     };
     if (og) pick_cb(std::true_type{});

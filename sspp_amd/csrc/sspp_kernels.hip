@@ -1287,6 +1287,7 @@ extern "C" int sspp_job_get_option(const sspp_job* j, int key, int64_t* value) {
         case SSPP_OPT_NPAIRS: *value = j->np_samp; return SSPP_OK;
         case SSPP_OPT_CYLBOX: *value = (j->cb_samp & sspk::kTableCylBox) != 0; return SSPP_OK;
         case SSPP_OPT_CAPSULE: *value = (j->cb_samp & sspk::kTableCapsule) != 0; return SSPP_OK;
+        case SSPP_OPT_CYLCYL: *value = (j->cb_samp & sspk::kTableCylCyl) != 0; return SSPP_OK;
         case SSPP_OPT_F32: *value = j->f32; return SSPP_OK;
         case SSPP_OPT_LAST_F32: *value = j->last_f32; return SSPP_OK;
         case SSPP_OPT_CREATE_US: *value = (int64_t)(j->create_ms * 1e3); return SSPP_OK;
