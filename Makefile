@@ -25,6 +25,9 @@ HDRS = include/sspp_hip.h $(SRC)/sspp_logtab.h $(SRC)/model.h $(SRC)/sspp_device
 # kernel instantiations, one translation unit per (dof, degree) (+ d0: TaskSpacePlanner), compiled
 # in parallel (one unit per degree also keeps the register allocation of each kernel its own)
 INST = $(OBJDIR)/sspp_inst_d0.o $(foreach d,1 2 3 4 6 7 9,$(foreach p,2 3,$(OBJDIR)/sspp_inst_d$(d)_p$(p).o))
+# the query launch's kernels (sspp_job_set_queries): units of their own, so that sharing one
+# leaves every other kernel's register allocation and code as they were
+INST += $(foreach d,1 2 3 4 6 7 9,$(foreach p,2 3,$(OBJDIR)/sspp_instq_d$(d)_p$(p).o))
 
 all: $(LIB) $(PYMOD) $(PYMOD2) oracle
 
@@ -43,6 +46,10 @@ $(OBJDIR)/sspp_inst_d0.o: $(SRC)/sspp_inst.hip $(HDRS)
 $(OBJDIR)/sspp_inst_d%.o: $(SRC)/sspp_inst.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
 	$(HIPCC) $(HIPFLAGS) -DSSPK_D=$(firstword $(subst _p, ,$*)) -DSSPK_P=$(lastword $(subst _p, ,$*)) -c $< -o $@
+
+$(OBJDIR)/sspp_instq_d%.o: $(SRC)/sspp_inst.hip $(HDRS)
+	@mkdir -p $(OBJDIR)
+	$(HIPCC) $(HIPFLAGS) -DSSPK_Q=1 -DSSPK_D=$(firstword $(subst _p, ,$*)) -DSSPK_P=$(lastword $(subst _p, ,$*)) -c $< -o $@
 
 # the source revision, compiled in as sspp_build_id() (sspp_amd/_stamp.py; checked at load time
 # by sspp_amd/_lib.py): rebuilt whenever any source changes

@@ -240,7 +240,9 @@ void sspp_job_free(sspp_job* job);
 #define SSPP_OPT_LAST_G1 8      /* get: phase-1 lanes per candidate of that launch              */
 #define SSPP_OPT_WP_ORDER 9     /* get: collision-waypoint order (0 bisection, 2 hit order)     */
 #define SSPP_OPT_PREPASS_US 10  /* get: host microseconds of the creation's hit-order pre-pass  */
-#define SSPP_OPT_NPAIRS 11      /* get: pairs in the sampled-candidate table                    */
+#define SSPP_OPT_NPAIRS 11      /* get: pairs in the sampled-candidate table (this and CYLBOX / CAPSULE /
+                                   CYLCYL: the table built last — the job's own, or after
+                                   sspp_job_set_queries the set's, until the next update)        */
 #define SSPP_OPT_CYLBOX 12      /* get: that table has cylinder-box pairs (k_sspp_c2f settles them) */
 #define SSPP_OPT_F32 13         /* k_sspp_c2f's FP32-filtered scan: 1 (default) on, 0 all-FP64.
                                    The filter only settles what FP64 settles the same way, so the
@@ -267,6 +269,8 @@ void sspp_job_free(sspp_job* job);
                                    that carry the capsule colliders run; mirrors SSPP_OPT_CYLBOX)  */
 #define SSPP_OPT_CYLCYL 25      /* get: the sampled-candidate table has cylinder-cylinder pairs
                                    (mirrors SSPP_OPT_CYLBOX / SSPP_OPT_CAPSULE)                    */
+#define SSPP_OPT_LAST_QUERIES 26 /* get: queries of the job's last launch (sspp_job_sample_score_queries);
+                                   0 for every other launch                                       */
 #define SSPP_OPT_TSP_REP 19     /* TaskSpacePlanner k_tsp form 3: sub-batches of candidates
                                    per workgroup (one prologue for all of them), 1..16, -1 by batch
                                    size; get: the last k_tsp launch's                            */
@@ -352,6 +356,28 @@ void sspp_ces_free(sspp_ces* ces);
 int sspp_job_update_sspp(sspp_job* job, const double* init_ctrl /* [n][D] */, double sigma,
                          const double* limits /* [D] */, uint64_t seed, void* stream);
 
+/* ---- query launches: many independent queries of one job in one k_sspp_c2f launch ----
+ * sspp_job_set_queries gives the job a set of 1 <= Q <= 64 queries that share its scene, knots,
+ * dof and check_points: query q has its own initial control points, sigma, limits and seed.
+ * The uploads are asynchronous on `stream` from job-owned staging (valid until the next set),
+ * and the job's single-query state (sspp_job_update_sspp's values, its pair tables, what
+ * sspp_job_sample_score computes) is left as it was.  The set's pair table keeps a pair that at
+ * least one query's candidates can reach.
+ * sspp_job_sample_score_queries is one launch: step q scores candidate ids
+ * [first_id, first_id + B) of query q into d_arc / d_feasible + q * B, d_ctrl_out + q * B * n * D
+ * and d_best[q] — bit for bit what sspp_job_update_sspp(query q) + sspp_job_sample_score(first_id,
+ * B) write.  Asynchronous, no synchronisation, no allocation after the first call of a size.
+ * Q is the last set's (SSPP_E_INVAL without one).  Query launches are never split
+ * (SSPP_OPT_LAST_SPLIT reads 0) and have no NT = 64 kernels: a forced SSPP_OPT_SHAPE_NT = 64 is
+ * refused with SSPP_E_INVAL.  No reference counterpart (the reference plans one query per call). */
+int sspp_job_set_queries(sspp_job* job, int Q, const double* init_ctrl /* [Q][n][D] */,
+                         const double* sigma /* [Q] */, const double* limits /* [Q][D] */,
+                         const uint64_t* seed /* [Q] */, void* stream);
+int sspp_job_sample_score_queries(sspp_job* job, int64_t first_id, int64_t B, double* d_arc /* [Q][B] */,
+                                  uint8_t* d_feasible /* [Q][B] */,
+                                  double* d_ctrl_out /* nullable [Q][B][n][D] */,
+                                  sspp_best* d_best /* nullable [Q] */, void* stream);
+
 /* ---- drop-in planner: SamplingPathPlanner<N> state kept on the device across calls ----
  * One object per `_sspp.SamplingPathPlannerN` (src/sspp_bindings.cpp:24-50): it owns a HIP
  * stream, the job of the last plan() shape (init_points, check_points, capacity) and the
@@ -372,6 +398,21 @@ int sspp_planner_plan(sspp_planner* p, const double* start, const double* end, d
                       uint64_t seed, int64_t first_id, double* knots_out, int64_t* n_feasible,
                       int64_t* feasible_ids, double* feasible_arc, double* feasible_ctrl,
                       sspp_best* best_out);
+/* Q >= 1 plan() calls that share sigma, limits and the shape (sample_count, check_points,
+ * init_points), scored as query launches of at most 64 queries each on the planner's stream with
+ * one synchronisation at the end.  Query q plans starts[q] -> ends[q] with seeds[q] over ids
+ * [first_id, first_id + sample_count).  Outputs: knots [init_points+4] (shared), best_out[q]
+ * (findBestPath: lowest arc, lowest id on ties; index -1 and cost +inf when nothing is feasible),
+ * best_ctrl_out[q] the winner's control points [n][D] (zeros without a winner; bit-equal to
+ * sspp_planner_plan's for that query), n_feasible[q], and every candidate's arc / feasible flag
+ * (nullable, [Q][sample_count]).  Uses a cached job of its own per shape: the plan() job and its
+ * buffers are not touched.                                                                     */
+int sspp_planner_plan_many(sspp_planner* p, int Q, const double* starts /* [Q][D] */,
+                           const double* ends /* [Q][D] */, double sigma, const double* limits /* [D] */,
+                           int sample_count, int check_points, int init_points,
+                           const uint64_t* seeds /* [Q] */, int64_t first_id, double* knots_out,
+                           sspp_best* best_out /* [Q] */, double* best_ctrl_out /* [Q][n][D] */,
+                           int64_t* n_feasible /* [Q] */, double* arc_out, uint8_t* feasible_out);
 int sspp_planner_score(sspp_planner* p, const double* knots, int degree,
                        const double* ctrl /* [B][n][D] */, int64_t B, int n, int W, int with_collision,
                        double* arc_out, uint8_t* feasible_out, sspp_best* best_out);

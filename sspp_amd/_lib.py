@@ -140,6 +140,11 @@ SIGNATURES = {
     "sspp_sample_ctrl_host": (C.c_int, [_d, _i, _d, _i, _i, C.c_double, _d, C.c_uint64, _i64,
                                         _i64, _d]),
     "sspp_job_update_sspp": (C.c_int, [_vp, _d, C.c_double, _d, C.c_uint64, _vp]),
+    "sspp_job_set_queries": (C.c_int, [_vp, _i, _d, _d, _d, C.POINTER(C.c_uint64), _vp]),
+    "sspp_job_sample_score_queries": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "sspp_planner_plan_many": (C.c_int, [_vp, _i, _d, _d, C.c_double, _d, _i, _i, _i, C.POINTER(C.c_uint64),
+                                         _i64, _d, C.POINTER(Best), _d, C.POINTER(_i64), _d,
+                                         C.POINTER(C.c_uint8)]),
     "sspp_planner_create": (C.c_int, [_vp, _i, C.POINTER(_vp)]),
     "sspp_planner_plan": (C.c_int, [_vp, _d, _d, C.c_double, _d, _i, _i, _i, C.c_uint64, _i64, _d,
                                     C.POINTER(_i64), C.POINTER(_i64), _d, _d, C.POINTER(Best)]),
@@ -174,6 +179,7 @@ OPT_SPLIT, OPT_LAST_SPLIT, OPT_TSP_REP = 17, 18, 19
 OPT_SPLIT_LINGER_US, OPT_SPLIT_DROP, OPT_SPLIT_HANDOFFS, OPT_SPLIT_LOST = 20, 21, 22, 23
 OPT_CAPSULE = 24
 OPT_CYLCYL = 25
+OPT_LAST_QUERIES = 26
 OPT_CES_FUSED = 101
 
 

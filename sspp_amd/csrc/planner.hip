@@ -15,6 +15,7 @@
 // include/sspp.h:215-216).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -102,10 +103,22 @@ struct sspp_planner {
     Pinned<unsigned char> h_sfeas;
     Pinned<sspp_best> h_sbest;
     Dev<double> d_in;
+    // plan_many(): a job of its own per shape (the plan() job and buffers stay as they are),
+    // device outputs of one chunk of queries, pinned results of the whole call
+    JobRef many_job;
+    int many_n = 0, many_W = 0;
+    int64_t many_cap = 0;
+    Dev<double> dm_arc, dm_ctrl;
+    Dev<unsigned char> dm_feas;
+    Dev<sspp_best> dm_best;
+    Pinned<sspp_best> hm_best;
+    Pinned<double> hm_ctrl, hm_arc;
+    Pinned<unsigned char> hm_feas;
     ~sspp_planner() {
         if (stream) (void)hipStreamSynchronize(stream);  // this planner's work on the shared stream
         plan_job.reset();
         score_job.reset();
+        many_job.reset();
     }
 };
 
@@ -238,6 +251,96 @@ extern "C" int sspp_planner_plan(sspp_planner* p, const double* start, const dou
     best_out->index = bi;
     best_out->count = cnt;
     best_out->reserved = 0;
+    return SSPP_OK;
+}
+
+// plan_many()'s gather: query q's argmin record and its winner's control-point row (zeros without
+// a winner) from the chunk's device outputs into the mapped pinned results
+__global__ __launch_bounds__(64) void k_gather_best(const sspp_best* __restrict__ best, const double* __restrict__ ctrl,
+                                                    long long first_id, long long B, int nd,
+                                                    sspp_best* __restrict__ best_out, double* __restrict__ ctrl_out) {
+    const int q = blockIdx.x;
+    const sspp_best b = best[q];
+    const long long c = b.index - first_id;
+    const bool ok = b.index >= 0 && c >= 0 && c < B;
+    for (int t = threadIdx.x; t < nd; t += 64) ctrl_out[(size_t)q * nd + t] = ok ? ctrl[((size_t)q * B + c) * nd + t] : 0.0;
+    if (threadIdx.x == 0) best_out[q] = b;
+}
+
+// device bytes of one chunk's control points (feasible rows only are written): larger sets go in
+// chunks of fewer queries
+constexpr size_t kManyCtrlBytes = (size_t)256 << 20;
+
+extern "C" int sspp_planner_plan_many(sspp_planner* p, int Q, const double* starts, const double* ends, double sigma,
+                                      const double* limits, int sample_count, int check_points, int init_points,
+                                      const uint64_t* seeds, int64_t first_id, double* knots_out, sspp_best* best_out,
+                                      double* best_ctrl_out, int64_t* n_feasible, double* arc_out,
+                                      uint8_t* feasible_out) {
+    sspp::clear_error();
+    if (!p || !starts || !ends || !limits || !seeds || !knots_out || !best_out || !best_ctrl_out || !n_feasible)
+        return sspp::set_error(SSPP_E_INVAL, "sspp_planner_plan_many: null argument");
+    if (Q < 1) return sspp::set_error(SSPP_E_INVAL, "sspp_planner_plan_many: Q must be >= 1");
+    const int n = init_points, D = p->D, deg = 3;
+    if (sample_count < 1) return sspp::set_error(SSPP_E_INVAL, "sample_count must be >= 1");
+    if (n < deg + 1) return sspp::set_error(SSPP_E_INVAL, "init_points must be >= 4 for a cubic spline");
+    if (check_points < 2) return sspp::set_error(SSPP_E_INVAL, "check_points must be >= 2");
+    // initializePath per query (include/sspp.h:82-97); the knot vector depends on n only
+    const size_t nd = (size_t)n * D;
+    const int64_t B = sample_count;
+    std::vector<double> u((size_t)n), pts(nd), ctrl0((size_t)Q * nd);
+    for (int i = 0; i < n; ++i) u[i] = (double)i / (n - 1);
+    for (int q = 0; q < Q; ++q) {
+        for (int i = 0; i < n; ++i)
+            for (int d = 0; d < D; ++d) pts[(size_t)i * D + d] = (1 - u[i]) * starts[(size_t)q * D + d] + u[i] * ends[(size_t)q * D + d];
+        if (sspp::interpolate(pts.data(), n, D, deg, u.data(), knots_out, ctrl0.data() + q * nd) != 0)
+            return sspp::set_error(SSPP_E_INVAL, "initializePath: interpolation failed");
+    }
+    const int chunk = (int)std::min<size_t>(64, std::max<size_t>(1, kManyCtrlBytes / (sizeof(double) * (size_t)B * nd)));
+    const int qc_max = std::min(Q, chunk);
+    int rc;
+    if (!p->many_job.j || p->many_n != n || p->many_W != check_points || B > p->many_cap) {
+        p->many_job.reset();
+        sspp_sspp_args a{};
+        a.knots = knots_out; a.degree = deg; a.init_ctrl = ctrl0.data(); a.n_ctrl = n; a.dof = D;
+        a.sigma = sigma; a.limits = limits; a.check_points = check_points; a.seed = seeds[0];
+        if ((rc = sspp::job_create_sspp_async(p->scene, &a, B, &p->many_job.j))) return rc;
+        p->many_n = n; p->many_W = check_points; p->many_cap = B;
+    }
+    if ((rc = p->dm_arc.reserve((size_t)qc_max * B)) || (rc = p->dm_feas.reserve((size_t)qc_max * B)) ||
+        (rc = p->dm_best.reserve(qc_max)) || (rc = p->dm_ctrl.reserve((size_t)qc_max * B * nd)) ||
+        (rc = p->hm_best.reserve(Q)) || (rc = p->hm_ctrl.reserve((size_t)Q * nd)) ||
+        (arc_out && (rc = p->hm_arc.reserve((size_t)Q * B))) || (feasible_out && (rc = p->hm_feas.reserve((size_t)Q * B))))
+        return rc;
+    sspp_best* hb = p->hm_best.dev();
+    double* hc = p->hm_ctrl.dev();
+    if (!hb || !hc) return sspp::set_error(SSPP_E_HIP, "hipHostGetDevicePointer failed");
+    sspp_job* j = p->many_job.j;
+    sspp::job_set_ctrl_feasible_only(j, 1);  // only a feasible candidate can win
+    std::vector<double> sig((size_t)qc_max, sigma), lim((size_t)qc_max * D);
+    for (int q = 0; q < qc_max; ++q) std::memcpy(lim.data() + (size_t)q * D, limits, sizeof(double) * D);
+    for (int q0 = 0; q0 < Q; q0 += chunk) {
+        const int qc = std::min(chunk, Q - q0);
+        if ((rc = sspp_job_set_queries(j, qc, ctrl0.data() + (size_t)q0 * nd, sig.data(), lim.data(), seeds + q0, p->stream)) ||
+            (rc = sspp_job_sample_score_queries(j, first_id, B, p->dm_arc.p, p->dm_feas.p, p->dm_ctrl.p, p->dm_best.p,
+                                                p->stream)))
+            return rc;
+        hipLaunchKernelGGL(k_gather_best, dim3(qc), dim3(64), 0, p->stream, p->dm_best.p, p->dm_ctrl.p, (long long)first_id,
+                           (long long)B, (int)nd, hb + q0, hc + (size_t)q0 * nd);
+        if ((rc = hipck(hipGetLastError(), "k_gather_best"))) return rc;
+        if (arc_out && (rc = hipck(hipMemcpyAsync(p->hm_arc.p + (size_t)q0 * B, p->dm_arc.p, sizeof(double) * qc * B,
+                                                  hipMemcpyDeviceToHost, p->stream), "copy arc")))
+            return rc;
+        if (feasible_out && (rc = hipck(hipMemcpyAsync(p->hm_feas.p + (size_t)q0 * B, p->dm_feas.p, (size_t)qc * B,
+                                                       hipMemcpyDeviceToHost, p->stream), "copy feasible")))
+            return rc;
+    }
+    if ((rc = hipck(hipStreamSynchronize(p->stream), "plan_many"))) return rc;
+    if ((rc = sspp_best_check(p->hm_best.p, Q))) return rc;
+    std::memcpy(best_out, p->hm_best.p, sizeof(sspp_best) * Q);
+    std::memcpy(best_ctrl_out, p->hm_ctrl.p, sizeof(double) * Q * nd);
+    for (int q = 0; q < Q; ++q) n_feasible[q] = best_out[q].count;
+    if (arc_out) std::memcpy(arc_out, p->hm_arc.p, sizeof(double) * Q * B);
+    if (feasible_out) std::memcpy(feasible_out, p->hm_feas.p, (size_t)Q * B);
     return SSPP_OK;
 }
 

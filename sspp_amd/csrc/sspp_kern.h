@@ -801,6 +801,17 @@ struct SurvPtrs {
     int shard_cap;     // slots per shard: shard s owns [s * shard_cap, (s + 1) * shard_cap)
 };
 
+// a query launch's per-step tables (k_sspp_c2f<..., QM = true>): step s of the launch is query s,
+// with its own initial spline, limits, sigma and seed (sspp_job_set_queries)
+struct QryPtrs {
+    const double* init;               // [Q][n][D]
+    const double* limits;             // [Q][D]
+    const double* sigma;              // [Q]
+    const unsigned long long* seed;   // [Q]
+};
+
+__device__ __forceinline__ const QryPtrs& qry_of(const QryPtrs& t) { return t; }
+
 struct SsppC2F {
     KScene sc;
     int has_scene;
@@ -1344,7 +1355,10 @@ __device__ __forceinline__ void surv_finish(const SsppC2F& a, const SceneT& TT, 
 // SPLIT: the split launch's instance (single-geom movers without cylinder-box pairs): phase 1,
 // then the survivor queue; the in-workgroup phases 2-4 are unreachable there and compiled out, so
 // the queue costs the unsplit instances no registers
-template <int D, int NM, int P, bool ONEGEOM, int NT, bool CBX, bool SPLIT = false>
+// QM: the query launch's instance (never split): the prologue takes the step's initial spline,
+// limits, sigma and seed from the tables of the one trailing argument (QryPtrs), which only these
+// instances have — the others' argument list, and so their code, is what it was without them
+template <int D, int NM, int P, bool ONEGEOM, int NT, bool CBX, bool SPLIT = false, bool QM = false, class... QA>
 __global__ __launch_bounds__(NT, (NT <= SSPP_C2F_FIVE_MAX && ONEGEOM) ? SSPP_C2F_WAVES_PER_EU : SSPP_C2F_WAVES_PER_EU_WIDE) void k_sspp_c2f(
     SsppC2F a, SceneT T, const double* __restrict__ otab, const float* __restrict__ otab32,
     const int* __restrict__ ospan,
@@ -1352,7 +1366,8 @@ __global__ __launch_bounds__(NT, (NT <= SSPP_C2F_FIVE_MAX && ONEGEOM) ? SSPP_C2F
     const double* __restrict__ init_ctrl, const double* __restrict__ limits,
     const double* __restrict__ ctrl_in, double* __restrict__ ctrl_out, double* __restrict__ arc,
     unsigned char* __restrict__ feasible, BlockBest* __restrict__ part, ArgminSync* sync, sspp_best* best,
-    SurvPtrs q) {
+    SurvPtrs q, QA... qq) {
+    static_assert(sizeof...(QA) == (QM ? 1 : 0) && !(QM && SPLIT), "query launches: one QryPtrs, never split");
     extern __shared__ __attribute__((aligned(16))) double smem[];
     constexpr int P1 = P + 1;
     constexpr int NB = 3 * NM;  // AABB extents per candidate (x, y, z per mover)
@@ -1419,6 +1434,15 @@ __global__ __launch_bounds__(NT, (NT <= SSPP_C2F_FIVE_MAX && ONEGEOM) ? SSPP_C2F
 #pragma unroll
     for (int r = 0; r < P1; ++r) N32_p1[r] = otab32[row_p1 * P1 + r];
     const int span_p1 = ospan[row_p1];
+    double sigma = a.sigma;
+    unsigned long long seed = a.seed;
+    if constexpr (QM) {  // this step's query
+        const QryPtrs qt = qry_of(qq...);
+        init_ctrl = qt.init + (long long)step * ndof;
+        limits = qt.limits + step * D;
+        sigma = qt.sigma[step];
+        seed = qt.seed[step];
+    }
     for (int rr = tid; rr < ndof; rr += NT) {
         const double v = init_ctrl[rr];
         smem[o_fix + rr] = v;
@@ -1451,7 +1475,7 @@ __global__ __launch_bounds__(NT, (NT <= SSPP_C2F_FIVE_MAX && ONEGEOM) ? SSPP_C2F
             double* dst = smem + o_own + sl * nrd;
             float* dst32 = f32 ? s_f32 + o_own + sl * nrd : nullptr;
             if (!(ABL & 1)) {
-                sample_item_to(a.sampler, a.seed, (unsigned long long)(first_id + cand0 + sl), m, nrd, D, a.sigma,
+                sample_item_to(a.sampler, seed, (unsigned long long)(first_id + cand0 + sl), m, nrd, D, sigma,
                                s_lim, base, dst, dst32);
             } else {
                 const int per = a.sampler ? 4 : 2;
@@ -2778,6 +2802,21 @@ struct sspp_job {
     unsigned* dbg_beacon = nullptr;     // SSPP_OPT_DEBUG_BEACONS (-DSSPP_DEBUG_PROGRESS builds)
     long long sq_cap = 0;               // survivors the buffers hold (x sq_nrd doubles each)
     int sq_nrd = 0;
+    // query launches (sspp_job_set_queries): the set's tables — init [Q][n][D] | limits [Q][D] |
+    // sigma [Q] | seed [Q] in one device block sized for kMaxSteps queries — and its pair table
+    // (a pair some query can reach); the single-query state above is not touched
+    int nq = 0;                         // queries of the last sspp_job_set_queries (0: none yet)
+    int last_queries = 0;               // queries of the last launch (0: an ordinary launch)
+    unsigned long long* d_qtab = nullptr;
+    DPair* d_pairs_q = nullptr;
+    std::vector<DPair> h_pairs_q;
+    int np_q = 0, cb_q = 0, og_q = 1;
+    double feps_q = 0.0;                // f32_eps of that table
+    int view_q = 0;                     // the job's most recently built sampled table is a set's: the
+                                        // get-options that describe "the sampled table" read it
+    unsigned char* h_qpin = nullptr;    // pinned source of the set's async copies
+    hipEvent_t q_ev = nullptr;          // recorded after them: the next set waits on it
+    bool q_pending = false;
 };
 
 
@@ -2905,6 +2944,41 @@ hipError_t launch_c2f(const SsppC2F& k, const sspp_job* j, const SsppPtrs& o, in
     return launch_c2f_nt<D, NM, P, 256>(k, j, o, nblk, st, q);
 }
 
+// query launches (k_sspp_c2f<..., QM = true>; sspp_job_set_queries): step s scores query s from
+// the tables of qq against the pair table of the set (k.sc, T).  Never split; the throughput and
+// latency workgroup sizes only (a forced NT = 64 is refused by the host before it gets here)
+template <int D, int NM, int P, int NT>
+hipError_t launch_c2f_q_nt(const SsppC2F& k, const sspp_job* j, const SsppPtrs& o, int nblk, hipStream_t st,
+                           const SceneT& T, const QryPtrs& qq) {
+    const double* atab = j->d_tab + (size_t)(j->W + 1) * (P + 1);
+    const int* aspan = j->d_span + (j->W + 1);
+    const SurvPtrs q{};
+#define SSPP_LAUNCH_C2F_Q(NMV, OGV, CBV)                                                                  \
+    hipLaunchKernelGGL((k_sspp_c2f<D, NMV, P, OGV, NT, CBV, false, true>), dim3(nblk), dim3(NT), k.lds, st, k, T, \
+                       j->d_otab, j->d_otab32, j->d_ospan, atab, aspan, qq.init, qq.limits, o.ctrl_in,    \
+                       o.ctrl_out, o.arc, o.feasible, j->d_part, j->d_sync, o.best, q, qq)
+    const bool og = NM == 1 && k.sc.onegeom && k.sc.npairs > 0;
+    if (og && k.sc.cylbox) SSPP_LAUNCH_C2F_Q(1, true, true);
+    else if (og) SSPP_LAUNCH_C2F_Q(1, true, false);
+    else if (k.sc.cylbox) SSPP_LAUNCH_C2F_Q(NM, false, true);
+    else SSPP_LAUNCH_C2F_Q(NM, false, false);
+#undef SSPP_LAUNCH_C2F_Q
+    return hipGetLastError();
+}
+template <int D, int P>
+hipError_t entry_c2f_q_p(const SsppC2F& k, const sspp_job* j, const SsppPtrs& o, int nblk, hipStream_t st,
+                         const SceneT& T, const QryPtrs& qq) {
+    if (k.split || o.ctrl_in || (k.nt != 128 && k.nt != 256)) return hipErrorInvalidValue;
+    if (j->nm == 2) {
+        if constexpr (D == 9)
+            return k.nt == 128 ? launch_c2f_q_nt<9, 2, P, 128>(k, j, o, nblk, st, T, qq)
+                               : launch_c2f_q_nt<9, 2, P, 256>(k, j, o, nblk, st, T, qq);
+        return hipErrorInvalidValue;
+    }
+    return k.nt == 128 ? launch_c2f_q_nt<D, 1, P, 128>(k, j, o, nblk, st, T, qq)
+                       : launch_c2f_q_nt<D, 1, P, 256>(k, j, o, nblk, st, T, qq);
+}
+
 // ---- per-dof entry points, instantiated one dof per translation unit (sspp_inst.hip, built
 // with -DSSPK_D=1..9) so the kernels compile in parallel; the host code (sspp_kernels.hip)
 // switches on the job's dof
@@ -2962,6 +3036,16 @@ hipError_t entry_c2f(const SsppC2F& k, const sspp_job* j, const SsppPtrs& o, int
     return entry_c2f_p<D, 3>(k, j, o, nblk, st);
 #else
     return j->p == 3 ? entry_c2f_p<D, 3>(k, j, o, nblk, st) : entry_c2f_p<D, 2>(k, j, o, nblk, st);
+#endif
+}
+template <int D>
+hipError_t entry_c2f_q(const SsppC2F& k, const sspp_job* j, const SsppPtrs& o, int nblk, hipStream_t st,
+                       const SceneT& T, const QryPtrs& qq) {
+#ifdef SSPP_DEV_ONLY
+    if (j->p != 3) return hipErrorInvalidValue;
+    return entry_c2f_q_p<D, 3>(k, j, o, nblk, st, T, qq);
+#else
+    return j->p == 3 ? entry_c2f_q_p<D, 3>(k, j, o, nblk, st, T, qq) : entry_c2f_q_p<D, 2>(k, j, o, nblk, st, T, qq);
 #endif
 }
 template <int D>
@@ -3065,6 +3149,10 @@ hipError_t entry_tsp_group(const TspK& k, const TspGoals& goals, const sspp_job*
     X template hipError_t entry_c2f_p<D, P>(const SsppC2F&, const sspp_job*, const SsppPtrs&, int, hipStream_t); \
     X template hipError_t entry_census_p<D, P>(const sspp_job*, int, unsigned long long, unsigned long long*,   \
                                                const DPair*, hipStream_t);
+// the query launch's kernels, translation units of their own (sspp_inst.hip with -DSSPK_Q)
+#define SSPK_QENTRY_DECL(X, D, P)                                                                         \
+    X template hipError_t entry_c2f_q_p<D, P>(const SsppC2F&, const sspp_job*, const SsppPtrs&, int, hipStream_t, \
+                                              const SceneT&, const QryPtrs&);
 #define SSPK_TSP_DECL(X)                                                                                  \
     X template hipError_t entry_tsp<0>(const TspK&, const sspp_job*, int, const double*, const double*,    \
                                        const double*, double*, double*, double*, double*, double*, uint8_t*, \

@@ -27,6 +27,20 @@ SSPK_ENTRY_DECL(extern, 7, 3)
 SSPK_ENTRY_DECL(extern, 9, 2)
 SSPK_ENTRY_DECL(extern, 9, 3)
 SSPK_TSP_DECL(extern)
+SSPK_QENTRY_DECL(extern, 1, 2)
+SSPK_QENTRY_DECL(extern, 1, 3)
+SSPK_QENTRY_DECL(extern, 2, 2)
+SSPK_QENTRY_DECL(extern, 2, 3)
+SSPK_QENTRY_DECL(extern, 3, 2)
+SSPK_QENTRY_DECL(extern, 3, 3)
+SSPK_QENTRY_DECL(extern, 4, 2)
+SSPK_QENTRY_DECL(extern, 4, 3)
+SSPK_QENTRY_DECL(extern, 6, 2)
+SSPK_QENTRY_DECL(extern, 6, 3)
+SSPK_QENTRY_DECL(extern, 7, 2)
+SSPK_QENTRY_DECL(extern, 7, 3)
+SSPK_QENTRY_DECL(extern, 9, 2)
+SSPK_QENTRY_DECL(extern, 9, 3)
 }  // namespace sspk
 #endif
 
@@ -620,12 +634,13 @@ static void pairs_by_hits(const sspp_scene* sc, std::vector<DPair>& pairs, const
 // those bounds, and a pair pair_may_touch rejects for that box (the moving geom's reach covers
 // any rotation) has no contact for any candidate of the job: it is dropped from the sample-mode
 // pair table (scored caller splines, sspp_job_score_ctrl, keep the full table).
-static std::vector<DPair> reachable_pairs(const sspp_scene* sc, const std::vector<DPair>& in,
-                                          const double* init_ctrl, int n, int D, int p, double sigma,
-                                          const double* limits, int sampler) {
+// reach_box: that AABB per mover; pairs_in_boxes: the pairs that may touch in at least one of
+// nbox such boxes (a query set keeps a pair some query can reach)
+struct ReachBox { double v[kMaxMovers][3]; };
+static void reach_box(const sspp_scene* sc, const double* init_ctrl, int n, int D, int p, double sigma,
+                      const double* limits, int sampler, double (*lo)[3], double (*hi)[3]) {
     const double zmax = (sampler ? 5.8 : 8.6) * (1.0 + 1e-9);
     const int nm = (int)sc->movers.size();
-    double lo[kMaxMovers][3], hi[kMaxMovers][3];
     for (int m = 0; m < nm && m < kMaxMovers; ++m)
         for (int d = 0; d < 3; ++d) {
             const int col = 7 * m + d;
@@ -640,13 +655,26 @@ static std::vector<DPair> reachable_pairs(const sspp_scene* sc, const std::vecto
             lo[m][d] = a - 1e-9;
             hi[m][d] = b + 1e-9;
         }
+}
+static std::vector<DPair> pairs_in_boxes(const sspp_scene* sc, const std::vector<DPair>& in, const ReachBox* lo,
+                                         const ReachBox* hi, int nbox) {
+    const int nm = (int)sc->movers.size();
     std::vector<DPair> out;
     for (const DPair& pr : in) {
         const DGeom& G = sc->geoms[pr.gm];
         const int m = (nm > 1 && G.mover == 1) ? 1 : 0;
-        if (pair_may_touch(pr, G, lo[m], hi[m])) out.push_back(pr);
+        bool keep = false;
+        for (int b = 0; b < nbox && !keep; ++b) keep = pair_may_touch(pr, G, lo[b].v[m], hi[b].v[m]);
+        if (keep) out.push_back(pr);
     }
     return out;
+}
+static std::vector<DPair> reachable_pairs(const sspp_scene* sc, const std::vector<DPair>& in,
+                                          const double* init_ctrl, int n, int D, int p, double sigma,
+                                          const double* limits, int sampler) {
+    ReachBox lo, hi;
+    reach_box(sc, init_ctrl, n, D, p, sigma, limits, sampler, lo.v, hi.v);
+    return pairs_in_boxes(sc, in, &lo, &hi, 1);
 }
 
 static void table_flags(const sspp_scene* sc, const std::vector<DPair>& t, int* np, int* cb, int* og) {
@@ -764,6 +792,7 @@ static int set_job_tables(sspp_job* j, const double* init_ctrl, double sigma, co
         }
     }
     j->pair_order = order;
+    j->view_q = 0;
     if (create) {
         j->wp_order = order == 2 ? 2 : 0;
         j->h_wps = wps;
@@ -1046,9 +1075,16 @@ static int survq_reserve(sspp_job* j, int64_t cands, int nrd) {
 
 static int run_sspp(sspp_job* j, const double* d_ctrl, int64_t first_id, int64_t B, double* d_arc,
                     uint8_t* d_feasible, double* d_ctrl_out, sspp_best* d_best, void* stream,
-                    int steps = 1, int64_t step_stride = 0) {
+                    int steps = 1, int64_t step_stride = 0, bool queries = false) {
     sspp::clear_error();
     if (!j || j->kind != 0) return sspp::set_error(SSPP_E_INVAL, "not a SamplingPathPlanner job");
+    if (queries) {  // step s is query s of the last sspp_job_set_queries; every step scores the same ids
+        if (j->nq < 1) return sspp::set_error(SSPP_E_INVAL, "sspp_job_sample_score_queries: no sspp_job_set_queries yet");
+        if (j->opt_nt == 64)
+            return sspp::set_error(SSPP_E_INVAL, "query launches have no NT = 64 kernels (SSPP_OPT_SHAPE_NT: 0, 128 or 256)");
+        steps = j->nq;
+        step_stride = 0;
+    }
     if (B < 1 || B > j->max_batch) return sspp::set_error(SSPP_E_INVAL, "batch size out of range");
     if (!d_arc || !d_feasible) return sspp::set_error(SSPP_E_INVAL, "null output");
     if (steps < 1 || steps > kMaxSteps || (steps > 1 && d_ctrl))
@@ -1084,6 +1120,7 @@ static int run_sspp(sspp_job* j, const double* d_ctrl, int64_t first_id, int64_t
     }
     SsppC2F c{};
     c.sc = kscene_job(j, d_ctrl == nullptr);
+    if (queries && j->d_pairs_q) { c.sc.npairs = j->np_q; c.sc.onegeom = j->og_q; c.sc.cylbox = j->cb_q; }
     c.has_scene = j->scene != nullptr && (c.sc.npairs > 0 || c.sc.static_block);
     c.sampler = j->sampler;
     c.p = p; c.n = n; c.W = j->W; c.sigma = j->sigma; c.seed = j->seed;
@@ -1096,7 +1133,8 @@ static int run_sspp(sspp_job* j, const double* d_ctrl, int64_t first_id, int64_t
     c.r0 = r0; c.r1 = r1;
     c.nt = nt; c.lds = (int)lds;
     c.ctrl_feas = j->ctrl_feas;
-    const double feps = j->f32 && c.has_scene ? f32_eps(j->scene, d_ctrl ? j->h_pairs : j->h_pairs_s) : 0.0;
+    const double feps = !(j->f32 && c.has_scene) ? 0.0
+                        : queries ? j->feps_q : f32_eps(j->scene, d_ctrl ? j->h_pairs : j->h_pairs_s);
     c.f32 = feps > 0.0 ? 1 : 0;
     c.feps = (float)feps;
     c.fplim = kF32PosLimit;
@@ -1106,7 +1144,9 @@ static int run_sspp(sspp_job* j, const double* d_ctrl, int64_t first_id, int64_t
     // splits only a launch that is one resident round (c2f_one_round)
     c.nsteps = steps;
     // (a split launch's arrival counters hold up to 65535 workgroups per shard in their low half)
-    c.split = j->opt_split && (int64_t)steps * B >= kSplitMinCands && !d_ctrl && !d_ctrl_out && !j->arc_all &&
+    // (never a query launch: the consumers finish other workgroups' survivors from their own copy
+    // of the fixed rows, which are per step there)
+    c.split = !queries && j->opt_split && (int64_t)steps * B >= kSplitMinCands && !d_ctrl && !d_ctrl_out && !j->arc_all &&
               (int64_t)nblk * steps < 65536 &&
               c.has_scene && c.sc.npairs > 0 && !c.sc.static_block && j->nm == 1 && c.sc.onegeom && !c.sc.cylbox &&
               cpb >= 3;  // the consumers' control words live in s_surv (cpb + 1 ints)
@@ -1131,6 +1171,28 @@ static int run_sspp(sspp_job* j, const double* d_ctrl, int64_t first_id, int64_t
     SsppPtrs o{d_ctrl, d_ctrl_out, d_arc, d_feasible, d_best, q, &split_used};
     const int nb = nblk * steps;
     hipError_t e = hipErrorInvalidValue;
+    j->last_queries = queries ? steps : 0;
+    if (queries) {
+        const size_t nd = (size_t)n * D, Q = (size_t)steps;
+        const double* qt = (const double*)j->d_qtab;
+        const QryPtrs qq{qt, qt + Q * nd, qt + Q * (nd + D), j->d_qtab + Q * (nd + D + 1)};
+        SceneT T = scene_t(j->scene);
+        if (j->d_pairs_q) { T.pairs = j->d_pairs_q; T.visit = nullptr; }
+        switch (j->D) {
+#ifndef SSPP_DEV_ONLY
+            case 1: e = entry_c2f_q<1>(c, j, o, nb, st, T, qq); break;
+            case 2: e = entry_c2f_q<2>(c, j, o, nb, st, T, qq); break;
+            case 3: e = entry_c2f_q<3>(c, j, o, nb, st, T, qq); break;
+            case 4: e = entry_c2f_q<4>(c, j, o, nb, st, T, qq); break;
+            case 6: e = entry_c2f_q<6>(c, j, o, nb, st, T, qq); break;
+            case 9: e = entry_c2f_q<9>(c, j, o, nb, st, T, qq); break;
+#endif
+            case 7: e = entry_c2f_q<7>(c, j, o, nb, st, T, qq); break;
+        }
+        j->last_split = 0;
+        if (e != hipSuccess) return hip_fail(e, "k_sspp_c2f query launch");
+        return SSPP_OK;
+    }
     switch (j->D) {
 #ifndef SSPP_DEV_ONLY
         case 1: e = entry_c2f<1>(c, j, o, nb, st); break;
@@ -1165,6 +1227,7 @@ extern "C" int sspp_job_update_sspp(sspp_job* j, const double* init_ctrl, double
     const size_t nd = (size_t)j->n * j->D;
     hipStream_t st = (hipStream_t)stream;
     j->seed = seed;  // a kernel argument: nothing to upload
+    j->view_q = 0;
     // the device tables depend only on (init_ctrl, sigma, limits): an update that repeats the
     // values the device holds (a planning loop re-planning the same query) uploads nothing
     if (j->h_stage.size() == nd + (size_t)j->D && j->sigma == sigma &&
@@ -1202,6 +1265,71 @@ extern "C" int sspp_job_update_sspp(sspp_job* j, const double* init_ctrl, double
     HIPCHK(hipEventRecord(j->upd_ev, st));
     j->upd_pending = true;
     return SSPP_OK;
+}
+
+// A query set for query launches: Q independent queries (initial spline, sigma, limits, seed each)
+// against this job's scene, knots and check_points.  Their values go to the job's query tables
+// (asynchronous, from job-owned pinned staging: valid until the next set), and the set's pair
+// table is the job's current table without the pairs no query can reach (reachable_pairs' test
+// per query; no census, no hit order).  The single-query state (sspp_job_update_sspp's) stays.
+extern "C" int sspp_job_set_queries(sspp_job* j, int Q, const double* init_ctrl, const double* sigma,
+                                    const double* limits, const uint64_t* seed, void* stream) {
+    sspp::clear_error();
+    if (!j || j->kind != 0 || !init_ctrl || !sigma || !limits || !seed)
+        return sspp::set_error(SSPP_E_INVAL, "sspp_job_set_queries: bad argument");
+    if (Q < 1 || Q > kMaxSteps) return sspp::set_error(SSPP_E_INVAL, "sspp_job_set_queries: 1..64 queries");
+    const size_t nd = (size_t)j->n * j->D, D = (size_t)j->D;
+    const sspp_scene* sc = j->scene;
+    const bool pairs = sc && !sc->pairs.empty();
+    const size_t vcap = sizeof(double) * kMaxSteps * (nd + D + 2);
+    const size_t pcap = pairs ? sizeof(DPair) * sc->pairs.size() : 0;
+    hipStream_t st = (hipStream_t)stream;
+    if (j->q_pending) {  // the staging is the source of the previous set's copies until they complete
+        HIPCHK(hipEventSynchronize(j->q_ev));
+        j->q_pending = false;
+    }
+    if (!j->d_qtab) {  // once per job, sized for kMaxSteps queries
+        HIPCHK(hipMalloc((void**)&j->d_qtab, vcap));
+        if (pairs) HIPCHK(hipMalloc((void**)&j->d_pairs_q, pcap));
+        HIPCHK(hipHostMalloc((void**)&j->h_qpin, vcap + pcap, hipHostMallocDefault));
+        HIPCHK(hipEventCreateWithFlags(&j->q_ev, hipEventDisableTiming));
+    }
+    double* hv = (double*)j->h_qpin;
+    const size_t nv = (size_t)Q * (nd + D + 2);
+    std::memcpy(hv, init_ctrl, sizeof(double) * Q * nd);
+    std::memcpy(hv + Q * nd, limits, sizeof(double) * Q * D);
+    std::memcpy(hv + Q * (nd + D), sigma, sizeof(double) * Q);
+    std::memcpy(hv + Q * (nd + D + 1), seed, sizeof(uint64_t) * Q);
+    HIPCHK(hipMemcpyAsync(j->d_qtab, hv, sizeof(double) * nv, hipMemcpyHostToDevice, st));
+    j->np_q = 0; j->cb_q = 0; j->og_q = 1; j->feps_q = 0.0;
+    j->h_pairs_q.clear();
+    if (pairs) {
+        std::vector<ReachBox> lo((size_t)Q), hi((size_t)Q);
+        for (int q = 0; q < Q; ++q)
+            reach_box(sc, init_ctrl + q * nd, j->n, j->D, j->p, sigma[q], limits + q * D, j->sampler, lo[q].v, hi[q].v);
+        j->h_pairs_q = pairs_in_boxes(sc, j->h_pairs.empty() ? sc->pairs : j->h_pairs, lo.data(), hi.data(), Q);
+        table_flags(sc, j->h_pairs_q, &j->np_q, &j->cb_q, &j->og_q);
+        j->feps_q = f32_eps(sc, j->h_pairs_q);
+        if (!j->h_pairs_q.empty()) {
+            unsigned char* pp = j->h_qpin + vcap;
+            std::memcpy(pp, j->h_pairs_q.data(), sizeof(DPair) * j->h_pairs_q.size());
+            HIPCHK(hipMemcpyAsync(j->d_pairs_q, pp, sizeof(DPair) * j->h_pairs_q.size(), hipMemcpyHostToDevice, st));
+        }
+    }
+    HIPCHK(hipEventRecord(j->q_ev, st));
+    j->q_pending = true;
+    j->nq = Q;
+    j->view_q = 1;
+    return SSPP_OK;
+}
+
+// One launch: step s scores ids [first_id, first_id + B) of query s (the last sspp_job_set_queries)
+// into d_arc / d_feasible [Q][B], d_ctrl_out [Q][B][n][D] and d_best [Q] (both nullable) — each
+// query's outputs are what sspp_job_update_sspp + sspp_job_sample_score give for it alone
+extern "C" int sspp_job_sample_score_queries(sspp_job* j, int64_t first_id, int64_t B, double* d_arc,
+                                             uint8_t* d_feasible, double* d_ctrl_out, sspp_best* d_best,
+                                             void* stream) {
+    return run_sspp(j, nullptr, first_id, B, d_arc, d_feasible, d_ctrl_out, d_best, stream, 1, 0, true);
 }
 
 extern "C" int sspp_job_score_ctrl(sspp_job* j, const double* d_ctrl, int64_t first_id, int64_t B,
@@ -1284,15 +1412,17 @@ extern "C" int sspp_job_get_option(const sspp_job* j, int key, int64_t* value) {
         case SSPP_OPT_LAST_G1: *value = j->last_g1; return SSPP_OK;
         case SSPP_OPT_WP_ORDER: *value = j->wp_order; return SSPP_OK;
         case SSPP_OPT_PREPASS_US: *value = (int64_t)(j->prepass_ms * 1e3); return SSPP_OK;
-        case SSPP_OPT_NPAIRS: *value = j->np_samp; return SSPP_OK;
-        case SSPP_OPT_CYLBOX: *value = (j->cb_samp & sspk::kTableCylBox) != 0; return SSPP_OK;
-        case SSPP_OPT_CAPSULE: *value = (j->cb_samp & sspk::kTableCapsule) != 0; return SSPP_OK;
-        case SSPP_OPT_CYLCYL: *value = (j->cb_samp & sspk::kTableCylCyl) != 0; return SSPP_OK;
+        // the sampled-candidate table built last: the job's own, or a query set's
+        case SSPP_OPT_NPAIRS: *value = j->view_q ? j->np_q : j->np_samp; return SSPP_OK;
+        case SSPP_OPT_CYLBOX: *value = ((j->view_q ? j->cb_q : j->cb_samp) & sspk::kTableCylBox) != 0; return SSPP_OK;
+        case SSPP_OPT_CAPSULE: *value = ((j->view_q ? j->cb_q : j->cb_samp) & sspk::kTableCapsule) != 0; return SSPP_OK;
+        case SSPP_OPT_CYLCYL: *value = ((j->view_q ? j->cb_q : j->cb_samp) & sspk::kTableCylCyl) != 0; return SSPP_OK;
         case SSPP_OPT_F32: *value = j->f32; return SSPP_OK;
         case SSPP_OPT_LAST_F32: *value = j->last_f32; return SSPP_OK;
         case SSPP_OPT_CREATE_US: *value = (int64_t)(j->create_ms * 1e3); return SSPP_OK;
         case SSPP_OPT_SPLIT: *value = j->opt_split; return SSPP_OK;
         case SSPP_OPT_LAST_SPLIT: *value = j->last_split; return SSPP_OK;
+        case SSPP_OPT_LAST_QUERIES: *value = j->last_queries; return SSPP_OK;
         case SSPP_OPT_SPLIT_LINGER_US: *value = j->opt_linger_us; return SSPP_OK;
         case SSPP_OPT_SPLIT_DROP: *value = j->opt_split_drop; return SSPP_OK;
         case SSPP_OPT_SPLIT_HANDOFFS:
@@ -1607,6 +1737,13 @@ extern "C" void sspp_job_free(sspp_job* j) {
         (void)hipEventDestroy(j->upd_ev);
     }
     if (j->h_pin) (void)hipHostFree(j->h_pin);
+    if (j->q_ev) {
+        (void)hipEventSynchronize(j->q_ev);
+        (void)hipEventDestroy(j->q_ev);
+    }
+    if (j->d_qtab) (void)hipFree(j->d_qtab);
+    if (j->d_pairs_q) (void)hipFree(j->d_pairs_q);
+    if (j->h_qpin) (void)hipHostFree(j->h_qpin);
     delete j;
 }
 

@@ -7,6 +7,7 @@
 //       -> (bool, list[SplineN])
 //   Spline{3,6,7,9}()  .ctrls() -> (N, n_ctrl) float64 view
 //   create_model_capsule(uint64), create_data_capsule(uint64)
+// Beyond the reference: .plan_many(starts, ends, ...) — many plan() queries in one launch.
 // Everything planner-side goes through the C ABI (include/sspp_hip.h) into the HIP kernels;
 // this file holds no numerics beyond argument marshalling.
 //
@@ -163,6 +164,65 @@ public:
         last_best_index = best.index;
         last_feasible_ids.assign(ids_buf_.begin(), ids_buf_.begin() + nf);
         return py::make_tuple(found, paths);
+    }
+
+    // Q plan() calls that share sigma, limits and the shape, scored as query launches of up to 64
+    // queries (sspp_planner_plan_many): result q is what plan(starts[q], ends[q], ...) finds with
+    // seed seeds[q] (default: this planner's seed).  Not the reference's API; plan()'s state
+    // (get_ctrl_pts, last_best_*, last_feasible_ids) is left as it was.
+    py::list plan_many(py::array_t<double, py::array::c_style | py::array::forcecast> starts,
+                       py::array_t<double, py::array::c_style | py::array::forcecast> ends, double sigma,
+                       py::array_t<double, py::array::forcecast> limits, int sample_count, int check_points,
+                       int init_points, py::object seeds) {
+        if (starts.ndim() != 2 || starts.shape(1) != N)
+            throw py::value_error("starts: expected shape (Q, " + std::to_string(N) + ")");
+        if (ends.ndim() != 2 || ends.shape(1) != N)
+            throw py::value_error("ends: expected shape (Q, " + std::to_string(N) + ")");
+        const int Q = (int)starts.shape(0);
+        if (Q < 1) throw py::value_error("plan_many needs at least one query");
+        if (ends.shape(0) != Q) throw py::value_error("starts and ends differ in the number of queries");
+        auto l = vec_of(limits, N, "limits");
+        std::vector<uint64_t> sd((size_t)Q, seed);
+        if (!seeds.is_none()) {
+            std::vector<uint64_t> given;
+            try { given = seeds.cast<std::vector<uint64_t>>(); }
+            catch (const py::cast_error&) { throw py::value_error("seeds: expected a sequence of non-negative integers"); }
+            if ((int)given.size() != Q) throw py::value_error("seeds: expected one seed per query");
+            sd = given;
+        }
+        if (sample_count < 1) throw py::value_error("sample_count must be >= 1");
+        if (init_points < 4) throw py::value_error("init_points must be >= 4");
+        if (check_points < 2) throw py::value_error("check_points must be >= 2");
+        auto lk = lock();
+        ensure_planner();
+        const int n = init_points;
+        const size_t nd = (size_t)n * N;
+        std::vector<double> knots((size_t)n + 4), ctrl((size_t)Q * nd);
+        std::vector<sspp_best> best((size_t)Q);
+        std::vector<int64_t> nf((size_t)Q);
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = sspp_planner_plan_many(planner_.get(), Q, starts.data(), ends.data(), sigma, l.data(), sample_count,
+                                        check_points, init_points, sd.data(), 0, knots.data(), best.data(), ctrl.data(),
+                                        nf.data(), nullptr, nullptr);
+        }
+        ck(rc, "plan_many");
+        py::object ns = py::module_::import("types").attr("SimpleNamespace");
+        py::list out;
+        for (int q = 0; q < Q; ++q) {
+            const bool found = best[q].index >= 0;
+            py::object path = py::none();
+            if (found) {
+                Spline<N> sp;
+                sp.set_from_nd(knots.data(), (int)knots.size(), ctrl.data() + (size_t)q * nd, n);
+                path = py::cast(std::move(sp));
+            }
+            using namespace py::literals;
+            out.append(ns("found"_a = found, "cost"_a = best[q].cost, "index"_a = best[q].index,
+                          "n_feasible"_a = nf[q], "path"_a = path));
+        }
+        return out;
     }
 
     py::array_t<double> evaluate(double u) const { return path_.eval(u); }
@@ -356,6 +416,9 @@ void bind(py::module& m, const std::string& planner_name, const std::string& spl
         .def("get_ctrl_pts", [](py::object self) { return self.cast<P&>().get_ctrl_pts(self); })
         .def("plan", &P::plan, py::arg("start"), py::arg("end"), py::arg("sigma"), py::arg("limits"),
              py::arg("sample_count") = 50, py::arg("check_points") = 50, py::arg("init_points") = 10)
+        .def("plan_many", &P::plan_many, py::arg("starts"), py::arg("ends"), py::arg("sigma"), py::arg("limits"),
+             py::arg("sample_count") = 50, py::arg("check_points") = 50, py::arg("init_points") = 10,
+             py::arg("seeds") = py::none())
         .def_readwrite("seed", &P::seed)
         .def_readonly("last_best_cost", &P::last_best_cost)
         .def_readonly("last_best_index", &P::last_best_index)

@@ -266,6 +266,51 @@ class SsppJob(_Job):
                                           _ptr(ctrl_out), _ptr(best), _stream(stream)),
               "sample_score")
 
+    def update(self, init_ctrl, sigma, limits, seed=DEFAULT_SEED, stream=None):
+        """Re-target the job to another query of the same shape (sspp_job_update_sspp)."""
+        init_ctrl = np.ascontiguousarray(np.asarray(init_ctrl, dtype=np.float64))
+        if init_ctrl.shape != (self.n, self.D):
+            raise ValueError("init_ctrl must be (%d, %d), got %s" % (self.n, self.D, init_ctrl.shape))
+        limits = _f64(limits, self.D)
+        check(lib().sspp_job_update_sspp(self._h, _dptr(init_ctrl), float(sigma), _dptr(limits),
+                                         int(seed) & (2 ** 64 - 1), _stream(stream)), "update")
+
+    def set_queries(self, init_ctrl, sigma, limits, seeds, stream=None):
+        """A set of Q queries for sample_score_queries (sspp_job_set_queries): init_ctrl
+        (Q, n, D), sigma (Q,), limits (Q, D), seeds (Q,).  The job's own query stays as it is."""
+        init_ctrl = np.ascontiguousarray(np.asarray(init_ctrl, dtype=np.float64))
+        if init_ctrl.ndim != 3 or init_ctrl.shape[1:] != (self.n, self.D):
+            raise ValueError("init_ctrl must be (Q, %d, %d), got %s" % (self.n, self.D, init_ctrl.shape))
+        Q = init_ctrl.shape[0]
+        sigma = _f64(sigma, Q)
+        limits = np.ascontiguousarray(np.asarray(limits, dtype=np.float64))
+        if limits.shape != (Q, self.D):
+            raise ValueError("limits must be (%d, %d), got %s" % (Q, self.D, limits.shape))
+        seeds = np.ascontiguousarray(np.asarray([int(s) & (2 ** 64 - 1) for s in np.asarray(seeds).reshape(-1)],
+                                                dtype=np.uint64))
+        if seeds.size != Q:
+            raise ValueError("expected %d seeds, got %d" % (Q, seeds.size))
+        check(lib().sspp_job_set_queries(self._h, Q, _dptr(init_ctrl), _dptr(sigma), _dptr(limits),
+                                         seeds.ctypes.data_as(C.POINTER(C.c_uint64)), _stream(stream)),
+              "set_queries")
+        self.n_queries = Q
+
+    def alloc_queries(self, Q, B, device="cuda", with_ctrl=False):
+        torch = _torch()
+        out = dict(arc=torch.empty((Q, B), dtype=torch.float64, device=device),
+                   feasible=torch.empty((Q, B), dtype=torch.uint8, device=device),
+                   best=torch.zeros((Q, 4), dtype=torch.int64, device=device))
+        if with_ctrl:
+            out["ctrl"] = torch.empty((Q, B, self.n, self.D), dtype=torch.float64, device=device)
+        return out
+
+    def sample_score_queries(self, first_id, B, arc, feasible, best=None, ctrl_out=None, stream=None):
+        """One launch for the whole set: row q of arc / feasible (Q, B), ctrl_out (Q, B, n, D) and
+        best (Q, 4) is what update(query q) + sample_score(first_id, B) give."""
+        check(lib().sspp_job_sample_score_queries(self._h, int(first_id), int(B), _ptr(arc), _ptr(feasible),
+                                                  _ptr(ctrl_out), _ptr(best), _stream(stream)),
+              "sample_score_queries")
+
     def score_ctrl(self, ctrl, first_id, arc, feasible, best, stream=None):
         B = ctrl.shape[0]
         check(lib().sspp_job_score_ctrl(self._h, _ptr(ctrl), int(first_id), int(B), _ptr(arc),
