@@ -3,10 +3,16 @@
 // The profiling hooks (sspp_prof.h), the build-time knobs (sspp_knobs.h), the dynamic LDS layouts
 // (sspp_lds.h) and the random numbers (sspp_rng.h) have headers of their own.
 // Included by sspp_kernels.hip (host side: scenes, jobs, the C ABI) and by sspp_inst.hip,
-// which the Makefile compiles once per dof (-DSSPK_D=1,2,3,4,6,7,9) and once for the
-// TaskSpacePlanner kernels (-DSSPK_D=0), each explicitly instantiating its entry points, so the
-// kernel instantiations compile in parallel.  Variant builds (tools/build_variant.sh, profiling
-// and ablation only) define SSPP_SINGLE_TU and instantiate everything in sspp_kernels.hip.
+// which the Makefile compiles once per (dof, degree) of SSPK_DP_LIST, once more per pair for the
+// query launch's kernels (-DSSPK_Q) and once for the TaskSpacePlanner kernels (-DSSPK_D=0), each
+// explicitly instantiating its entry points, so the kernel instantiations compile in parallel.
+// Variant builds (tools/build_variant.sh, profiling and ablation only) define SSPP_SINGLE_TU and
+// instantiate everything in sspp_kernels.hip.
+//
+// Host side of a launch, at the end of this file: sspp_scene and sspp_job; PairTable (a job holds
+// three: launch_table picks a launch's, table_set derives its flags and FP32 margin); one launch
+// chain for k_sspp_c2f (entry_c2f_p -> launch_c2f -> launch_c2f_nt, the query launch's QryPtrs as a
+// trailing pack); dispatch_dp, the one place that maps a job's (dof, degree) to an instantiation.
 //
 // Hot path (reference include/sspp.h:194-225 and include/sspp/tsp_planner.h:95-138):
 //   candidate sampling -> B-spline evaluation -> free-joint FK -> collision -> cost -> argmin.
@@ -48,7 +54,7 @@ namespace sspk {
 
 constexpr int kMaxMovers = 2;
 
-// what a pair contributes to its table's kernel selection (KScene::cylbox, sspp_job::cb_*)
+// what a pair contributes to its table's kernel selection (KScene::cylbox, PairTable::cb)
 constexpr int kTableCylBox = 1, kTableCapsule = 2, kTableCylCyl = 4;
 __host__ __device__ inline int table_bits(int tg, int to) {
     return (((tg == 5 && to == 6) || (tg == 6 && to == 5)) ? kTableCylBox : 0) |
@@ -2714,6 +2720,63 @@ struct sspp_scene {
     int device = 0;
 };
 
+// A pair table: the pairs one launch scans, in scan order, on the host and on the device, with what
+// the host derives from them — the kernel selection (KScene's npairs / cylbox / onegeom) and the
+// FP32 filter's margin.  table_set fills all of it but the device copy, which the owner uploads.
+struct PairTable {
+    std::vector<DPair> h;
+    DPair* d = nullptr;
+    int np = 0, cb = 0, og = 1;  // pairs, table_bits of them all, one moving geom
+    double feps = 0.0;           // f32_eps (0: the launch runs without the FP32 filter)
+};
+// a job's tables: every pair of the scene that can matter, for caller splines (full); without the
+// pairs no sampled candidate can reach (sampled); without those no query of a set can reach
+enum { kPairsFull = 0, kPairsSampled = 1, kPairsQueries = 2, kPairTables = 3 };
+
+// the flags of a pair list (a PairTable's, and the scene's own pairs for kscene)
+inline void pair_flags(const std::vector<DGeom>& geoms, const std::vector<DPair>& t, int* np, int* cb, int* og) {
+    *np = (int)t.size();
+    *cb = 0;
+    *og = 1;
+    for (const DPair& pr : t) {
+        *cb |= sspk::table_bits(geoms[pr.gm].type, pr.otype);
+        *og &= pr.gm == t[0].gm;
+    }
+}
+
+// The FP32 filter's certified margin for a pair table (sspp_filter.h): FP32's error
+// on a separation grows with the pair's extent (centre distance and box extents are bounded by
+// the two bounding radii plus the margin for every pair that passes the sphere test), about 6e-5 m
+// per metre of extent; eps = 2e-4 m per metre, at least 2e-4.  0 (filter off) past 64 pairs or
+// for pairs larger than 8 m, where the certified range would not be worth it.
+constexpr double kF32EpsPerMetre = 2e-4;
+constexpr float kF32PosLimit = 8.0f;
+inline double f32_eps(const sspp_scene* sc, const std::vector<DPair>& t) {
+    if (!sc || t.empty() || t.size() > 64) return 0.0;
+    double S = 1.0;
+    for (const DPair& pr : t) {
+        const DGeom& G = sc->geoms[pr.gm];
+        // the moving geom's offset from its mover's root scales the FP32 pose error like an extent
+        double gofs = 0.0, far = 0.0;
+        for (int k = 0; k < 3; ++k) gofs += G.pos[k] * G.pos[k];
+        gofs = std::sqrt(gofs);
+        const double ext = G.rbound + pr.orbound + pr.margin + gofs;
+        for (int k = 0; k < 3; ++k) far = std::max(far, std::fabs(pr.opos[k]));
+        if (!(ext <= 8.0) || !(far <= 2.0 * kF32PosLimit) || G.rbound <= 0.0) return 0.0;
+        S = std::max(S, ext);
+    }
+    return kF32EpsPerMetre * S;
+}
+
+// a table's pairs, and everything derived from them (sc may be null for an empty list)
+inline void table_set(PairTable& t, const sspp_scene* sc, std::vector<DPair> pairs) {
+    t.h = std::move(pairs);
+    t.np = t.cb = 0;
+    t.og = 1;
+    if (!t.h.empty()) pair_flags(sc->geoms, t.h, &t.np, &t.cb, &t.og);
+    t.feps = f32_eps(sc, t.h);
+}
+
 struct sspp_job {
     int kind = 0;  // 0 sspp, 1 tsp
     const sspp_scene* scene = nullptr;
@@ -2749,13 +2812,10 @@ struct sspp_job {
     float* d_otab32 = nullptr; // the same rows in FP32 (k_sspp_c2f's filtered scan)
     int* d_ospan = nullptr;
     std::vector<int> h_wps;    // that order
-    DPair* d_pairs = nullptr;  // this job's pair table (ordered)
-    DPair* d_pairs_s = nullptr;  // the same without the pairs no sampled candidate can reach
-    int np_full = 0, np_samp = 0, cb_full = 0, cb_samp = 0, og_full = 1, og_samp = 1;
+    PairTable tab[kPairTables];  // this job's pair tables (launch_table picks a launch's)
     ArgminSync* d_sync = nullptr;  // sharded arrival counters of the fused argmin [kMaxSteps]
     std::vector<double> h_knots;   // host copies: the knot vector, and the values the device
     std::vector<double> h_stage;   // holds (init | limits; sspp_job_update_sspp skips equal updates)
-    std::vector<DPair> h_pairs, h_pairs_s;
     int ctrl_feas = 0;               // k_sspp_c2f writes ctrl_out rows of feasible candidates only
     // TaskSpacePlanner options (sspp_job_set_option): evaluation form (-1 automatic, 0 k_tsp,
     // 1 k_tsp_pp, 2 k_tsp_pp2) and the generic (non-upright) narrowphase
@@ -2777,7 +2837,8 @@ struct sspp_job {
     std::thread prepass_thread;
     std::atomic<int> prepass_state{0};  // 0 none, 1 running, 2 result ready, 3 applied or dropped
     std::vector<int> pre_wps;           // the thread's result: waypoint order,
-    std::vector<DPair> pre_pairs, pre_pairs_s;  // pair tables (hit order) for the creation's values
+    PairTable pre[2];                   // full and sampled tables (hit order; host side only) for
+                                        // the creation's values
     double pre_ms = 0.0;                // census + host ordering, wall time
     int pre_gen = 0;                    // tables_gen the result was computed for
     int tables_gen = 0;                 // bumped by every update that re-derives the pair tables
@@ -2804,14 +2865,10 @@ struct sspp_job {
     int sq_nrd = 0;
     // query launches (sspp_job_set_queries): the set's tables — init [Q][n][D] | limits [Q][D] |
     // sigma [Q] | seed [Q] in one device block sized for kMaxSteps queries — and its pair table
-    // (a pair some query can reach); the single-query state above is not touched
+    // (tab[kPairsQueries]: a pair some query can reach); the single-query state above is not touched
     int nq = 0;                         // queries of the last sspp_job_set_queries (0: none yet)
     int last_queries = 0;               // queries of the last launch (0: an ordinary launch)
     unsigned long long* d_qtab = nullptr;
-    DPair* d_pairs_q = nullptr;
-    std::vector<DPair> h_pairs_q;
-    int np_q = 0, cb_q = 0, og_q = 1;
-    double feps_q = 0.0;                // f32_eps of that table
     int view_q = 0;                     // the job's most recently built sampled table is a set's: the
                                         // get-options that describe "the sampled table" read it
     unsigned char* h_qpin = nullptr;    // pinned source of the set's async copies
@@ -2826,9 +2883,7 @@ namespace sspk {
 inline KScene kscene(const sspp_scene* s, bool tsp, bool generic = false) {
     KScene k{};
     if (!s) return k;
-    k.npairs = (int)s->pairs.size();
-    k.onegeom = 1;
-    for (const DPair& p : s->pairs) k.onegeom &= (p.gm == s->pairs[0].gm);
+    pair_flags(s->geoms, s->pairs, &k.npairs, &k.cylbox, &k.onegeom);
     k.static_block = (!tsp && s->count_static && s->static_contacts > 0) ? 1 : 0;
     k.static_cost = tsp ? s->static_cost : 0.0;
     k.upright = (tsp && !generic) ? 1 : 0;
@@ -2836,7 +2891,6 @@ inline KScene kscene(const sspp_scene* s, bool tsp, bool generic = false) {
     for (const DPair& p : s->pairs) {
         const DGeom& g = s->geoms[p.gm];
         const int tg = g.type;
-        k.cylbox |= table_bits(tg, p.otype);
         // capsule pairs ride in the generic instantiations (CB = 1, no upright shortcuts)
         if (sspd::pair_has_capsule(tg, p.otype)) k.upright = k.cbup = 0;
         // the mover's yaw rotation keeps m[2] = m[5] = m[6] = m[7] = 0 exactly (mover_poses
@@ -2874,19 +2928,21 @@ struct SsppPtrs {
     int* split_used = nullptr;  // out: whether the launch was split (one resident round only)
 };
 
-// the job's pair table: sampled candidates use the reachable subset, caller splines the full one
-inline SceneT scene_t_job(const sspp_job* j, bool sampled) {
-    SceneT t = scene_t(j->scene);
-    if (j->d_pairs) { t.pairs = sampled ? j->d_pairs_s : j->d_pairs; t.visit = nullptr; }  // (another order)
-    return t;
+// the table of a launch: caller splines scan the full table, sampled candidates the reachable
+// subset, a query launch its set's
+inline const PairTable& launch_table(const sspp_job* j, bool ctrl_in, bool queries) {
+    return j->tab[queries ? kPairsQueries : ctrl_in ? kPairsFull : kPairsSampled];
 }
-inline KScene kscene_job(const sspp_job* j, bool sampled) {
+// the kernel's view of the scene with table t.  A table without a device copy (no scene, or a scene
+// without pairs) leaves the scene's own values.
+inline SceneT scene_t_job(const sspp_job* j, const PairTable& t) {
+    SceneT s = scene_t(j->scene);
+    if (t.d) { s.pairs = t.d; s.visit = nullptr; }  // (another order)
+    return s;
+}
+inline KScene kscene_job(const sspp_job* j, const PairTable& t) {
     KScene k = kscene(j->scene, false);
-    if (j->d_pairs) {
-        k.npairs = sampled ? j->np_samp : j->np_full;
-        k.onegeom = sampled ? j->og_samp : j->og_full;
-        k.cylbox = sampled ? j->cb_samp : j->cb_full;
-    }
+    if (t.d) { k.npairs = t.np; k.onegeom = t.og; k.cylbox = t.cb; }
     return k;
 }
 
@@ -2908,27 +2964,40 @@ inline bool c2f_one_round(const sspp_job* j, const void* fn, int nt, int lds, in
     return nblk <= c_wgs;
 }
 
-template <int D, int NM, int P, int NT>
+// The launch of k_sspp_c2f: launch_c2f picks the workgroup size, launch_c2f_nt the instantiation for
+// table t's flags (k.sc).  A query launch (sspp_job_set_queries) carries its QryPtrs as the trailing
+// pack, as the kernel does (QM): step s scores query s from those tables.  Query launches are never
+// split and have the throughput and latency workgroup sizes only, so the pack decides at compile
+// time which instantiations a translation unit holds.
+template <int D, int NM, int P, int NT, class... Q>
 hipError_t launch_c2f_nt(const SsppC2F& k, const sspp_job* j, const SsppPtrs& o, int nblk, hipStream_t st,
-                         const SurvPtrs& q) {
+                         const PairTable& t, const Q&... qq) {
+    constexpr bool QM = sizeof...(Q) != 0;
     const double* atab = j->d_tab + (size_t)(j->W + 1) * (P + 1);
     const int* aspan = j->d_span + (j->W + 1);
-    const SceneT T = scene_t_job(j, !o.ctrl_in);
+    const SceneT T = scene_t_job(j, t);
+    const double *init = j->d_init, *limits = j->d_limits;
+    if constexpr (QM) [&](const QryPtrs& qt) { init = qt.init; limits = qt.limits; }(qq...);
 #define SSPP_LAUNCH_C2F(NMV, OGV, CBV, SPV)                                                               \
     do {                                                                                                  \
         SsppC2F kk = k;                                                                                   \
         kk.split = SPV;                                                                                   \
         if (o.split_used) *o.split_used = SPV;                                                            \
-        hipLaunchKernelGGL((k_sspp_c2f<D, NMV, P, OGV, NT, CBV, SPV>), dim3(nblk), dim3(NT), kk.lds, st, kk, T, \
-                           j->d_otab, j->d_otab32, j->d_ospan, atab, aspan, j->d_init, j->d_limits, o.ctrl_in,   \
-                           o.ctrl_out, o.arc, o.feasible, j->d_part, j->d_sync, o.best, q);              \
+        hipLaunchKernelGGL((k_sspp_c2f<D, NMV, P, OGV, NT, CBV, SPV, QM, Q...>), dim3(nblk), dim3(NT), kk.lds, st, \
+                           kk, T, j->d_otab, j->d_otab32, j->d_ospan, atab, aspan, init, limits, o.ctrl_in, \
+                           o.ctrl_out, o.arc, o.feasible, j->d_part, j->d_sync, o.best, o.q, qq...);     \
     } while (0)
     const bool og = NM == 1 && k.sc.onegeom && k.sc.npairs > 0;
     if (og && k.sc.cylbox) SSPP_LAUNCH_C2F(1, true, true, false);
-    else if (og && k.split && c2f_one_round(j, (const void*)k_sspp_c2f<D, 1, P, true, NT, false, true>, NT, k.lds, nblk))
-        SSPP_LAUNCH_C2F(1, true, false, true);
-    else if (og) SSPP_LAUNCH_C2F(1, true, false, false);
-    else if (k.sc.cylbox) SSPP_LAUNCH_C2F(NM, false, true, false);
+    else if (og) {
+        if constexpr (!QM) {
+            if (k.split && c2f_one_round(j, (const void*)k_sspp_c2f<D, 1, P, true, NT, false, true>, NT, k.lds, nblk)) {
+                SSPP_LAUNCH_C2F(1, true, false, true);
+                return hipGetLastError();
+            }
+        }
+        SSPP_LAUNCH_C2F(1, true, false, false);
+    } else if (k.sc.cylbox) SSPP_LAUNCH_C2F(NM, false, true, false);
     else SSPP_LAUNCH_C2F(NM, false, false, false);
 #undef SSPP_LAUNCH_C2F
     return hipGetLastError();
@@ -2936,58 +3005,26 @@ hipError_t launch_c2f_nt(const SsppC2F& k, const sspp_job* j, const SsppPtrs& o,
 
 // three workgroup sizes: one- and two-wave workgroups (throughput shapes) and 4-wave workgroups
 // (a single plan() batch, latency shape); DESIGN.md §5
-template <int D, int NM, int P>
-hipError_t launch_c2f(const SsppC2F& k, const sspp_job* j, const SsppPtrs& o, int nblk, hipStream_t st) {
-    const SurvPtrs q = o.q;
-    if (k.nt == 64) return launch_c2f_nt<D, NM, P, 64>(k, j, o, nblk, st, q);
-    if (k.nt == 128) return launch_c2f_nt<D, NM, P, 128>(k, j, o, nblk, st, q);
-    return launch_c2f_nt<D, NM, P, 256>(k, j, o, nblk, st, q);
-}
-
-// query launches (k_sspp_c2f<..., QM = true>; sspp_job_set_queries): step s scores query s from
-// the tables of qq against the pair table of the set (k.sc, T).  Never split; the throughput and
-// latency workgroup sizes only (a forced NT = 64 is refused by the host before it gets here)
-template <int D, int NM, int P, int NT>
-hipError_t launch_c2f_q_nt(const SsppC2F& k, const sspp_job* j, const SsppPtrs& o, int nblk, hipStream_t st,
-                           const SceneT& T, const QryPtrs& qq) {
-    const double* atab = j->d_tab + (size_t)(j->W + 1) * (P + 1);
-    const int* aspan = j->d_span + (j->W + 1);
-    const SurvPtrs q{};
-#define SSPP_LAUNCH_C2F_Q(NMV, OGV, CBV)                                                                  \
-    hipLaunchKernelGGL((k_sspp_c2f<D, NMV, P, OGV, NT, CBV, false, true>), dim3(nblk), dim3(NT), k.lds, st, k, T, \
-                       j->d_otab, j->d_otab32, j->d_ospan, atab, aspan, qq.init, qq.limits, o.ctrl_in,    \
-                       o.ctrl_out, o.arc, o.feasible, j->d_part, j->d_sync, o.best, q, qq)
-    const bool og = NM == 1 && k.sc.onegeom && k.sc.npairs > 0;
-    if (og && k.sc.cylbox) SSPP_LAUNCH_C2F_Q(1, true, true);
-    else if (og) SSPP_LAUNCH_C2F_Q(1, true, false);
-    else if (k.sc.cylbox) SSPP_LAUNCH_C2F_Q(NM, false, true);
-    else SSPP_LAUNCH_C2F_Q(NM, false, false);
-#undef SSPP_LAUNCH_C2F_Q
-    return hipGetLastError();
-}
-template <int D, int P>
-hipError_t entry_c2f_q_p(const SsppC2F& k, const sspp_job* j, const SsppPtrs& o, int nblk, hipStream_t st,
-                         const SceneT& T, const QryPtrs& qq) {
-    if (k.split || o.ctrl_in || (k.nt != 128 && k.nt != 256)) return hipErrorInvalidValue;
-    if (j->nm == 2) {
-        if constexpr (D == 9)
-            return k.nt == 128 ? launch_c2f_q_nt<9, 2, P, 128>(k, j, o, nblk, st, T, qq)
-                               : launch_c2f_q_nt<9, 2, P, 256>(k, j, o, nblk, st, T, qq);
-        return hipErrorInvalidValue;
+template <int D, int NM, int P, class... Q>
+hipError_t launch_c2f(const SsppC2F& k, const sspp_job* j, const SsppPtrs& o, int nblk, hipStream_t st,
+                      const PairTable& t, const Q&... qq) {
+    if constexpr (sizeof...(Q) == 0) {
+        if (k.nt == 64) return launch_c2f_nt<D, NM, P, 64>(k, j, o, nblk, st, t);
     }
-    return k.nt == 128 ? launch_c2f_q_nt<D, 1, P, 128>(k, j, o, nblk, st, T, qq)
-                       : launch_c2f_q_nt<D, 1, P, 256>(k, j, o, nblk, st, T, qq);
+    if (k.nt == 128) return launch_c2f_nt<D, NM, P, 128>(k, j, o, nblk, st, t, qq...);
+    return launch_c2f_nt<D, NM, P, 256>(k, j, o, nblk, st, t, qq...);
 }
 
-// ---- per-dof entry points, instantiated one dof per translation unit (sspp_inst.hip, built
-// with -DSSPK_D=1..9) so the kernels compile in parallel; the host code (sspp_kernels.hip)
-// switches on the job's dof
+// ---- entry points, instantiated one (dof, degree) per translation unit (sspp_inst.hip, built with
+// -DSSPK_D=1..9 -DSSPK_P=2,3) so the kernels compile in parallel; the host code (sspp_kernels.hip)
+// reaches them through dispatch_dp
 // the hit census of a sampled job (k_sspp_census): M candidates, every collision waypoint
 template <int D, int NM, int P>
 hipError_t launch_census(const sspp_job* j, int M, unsigned long long seed, unsigned long long* d_hits,
                          const DPair* pairs, hipStream_t st) {
-    const KScene sc = kscene_job(j, true);
-    SceneT T = scene_t_job(j, true);
+    const PairTable& t = launch_table(j, false, false);
+    const KScene sc = kscene_job(j, t);
+    SceneT T = scene_t_job(j, t);
     if (pairs) { T.pairs = pairs; T.visit = nullptr; }  // the asynchronous pre-pass's own copy of the sampled table
     const int r0 = std::min(P, j->n), r1 = std::max(r0, j->n - P);
     const size_t lds = (size_t)census_layout(j->n, D, (r1 - r0) * D).bytes;
@@ -3012,13 +3049,17 @@ hipError_t launch_census(const sspp_job* j, int M, unsigned long long seed, unsi
 
 // one (dof, degree) per translation unit: sharing a unit with the other degree's kernels changed
 // the register allocation of the robocrane kernel (0 -> 275 spilled VGPRs at the same source)
-template <int D, int P>
-hipError_t entry_c2f_p(const SsppC2F& k, const sspp_job* j, const SsppPtrs& o, int nblk, hipStream_t st) {
+template <int D, int P, class... Q>
+hipError_t entry_c2f_p(const SsppC2F& k, const sspp_job* j, const SsppPtrs& o, int nblk, hipStream_t st,
+                       const PairTable& t, const Q&... qq) {
+    if constexpr (sizeof...(Q) != 0) {  // what a query launch has no kernels for
+        if (k.split || o.ctrl_in || (k.nt != 128 && k.nt != 256)) return hipErrorInvalidValue;
+    }
     if (j->nm == 2) {
-        if constexpr (D == 9) return launch_c2f<9, 2, P>(k, j, o, nblk, st);
+        if constexpr (D == 9) return launch_c2f<9, 2, P>(k, j, o, nblk, st, t, qq...);
         return hipErrorInvalidValue;
     }
-    return launch_c2f<D, 1, P>(k, j, o, nblk, st);
+    return launch_c2f<D, 1, P>(k, j, o, nblk, st, t, qq...);
 }
 template <int D, int P>
 hipError_t entry_census_p(const sspp_job* j, int M, unsigned long long seed, unsigned long long* d_hits,
@@ -3029,35 +3070,33 @@ hipError_t entry_census_p(const sspp_job* j, int M, unsigned long long seed, uns
     }
     return launch_census<D, 1, P>(j, M, seed, d_hits, pairs, st);
 }
-template <int D>
-hipError_t entry_c2f(const SsppC2F& k, const sspp_job* j, const SsppPtrs& o, int nblk, hipStream_t st) {
-#ifdef SSPP_DEV_ONLY  // variant builds for experiments: degree 3 only (fast compile)
-    if (j->p != 3) return hipErrorInvalidValue;
-    return entry_c2f_p<D, 3>(k, j, o, nblk, st);
+
+// The (dof, degree) pairs the SamplingPathPlanner kernels are built for, written once: the explicit
+// instantiations' declarations, the dispatcher and the job's dof check come from this list (the
+// Makefile's INST lists repeat it: make cannot read it).
+#define SSPK_DP_LIST(X) \
+    X(1, 2) X(1, 3) X(2, 2) X(2, 3) X(3, 2) X(3, 3) X(4, 2) X(4, 3) X(6, 2) X(6, 3) X(7, 2) X(7, 3) X(9, 2) X(9, 3)
+#ifdef SSPP_DEV_ONLY  // variant builds for experiments: dof 7, degree 3 only (fast compile)
+constexpr bool kDevOnly = true;
 #else
-    return j->p == 3 ? entry_c2f_p<D, 3>(k, j, o, nblk, st) : entry_c2f_p<D, 2>(k, j, o, nblk, st);
+constexpr bool kDevOnly = false;
 #endif
+inline bool dof_supported(int D) {
+#define SSPK_DP_IS(d, p) || D == d
+    return false SSPK_DP_LIST(SSPK_DP_IS);
+#undef SSPK_DP_IS
 }
-template <int D>
-hipError_t entry_c2f_q(const SsppC2F& k, const sspp_job* j, const SsppPtrs& o, int nblk, hipStream_t st,
-                       const SceneT& T, const QryPtrs& qq) {
-#ifdef SSPP_DEV_ONLY
-    if (j->p != 3) return hipErrorInvalidValue;
-    return entry_c2f_q_p<D, 3>(k, j, o, nblk, st, T, qq);
-#else
-    return j->p == 3 ? entry_c2f_q_p<D, 3>(k, j, o, nblk, st, T, qq) : entry_c2f_q_p<D, 2>(k, j, o, nblk, st, T, qq);
-#endif
-}
-template <int D>
-hipError_t entry_census(const sspp_job* j, int M, unsigned long long seed, unsigned long long* d_hits,
-                        const DPair* pairs, hipStream_t st) {
-#ifdef SSPP_DEV_ONLY
-    if (j->p != 3) return hipErrorInvalidValue;
-    return entry_census_p<D, 3>(j, M, seed, d_hits, pairs, st);
-#else
-    return j->p == 3 ? entry_census_p<D, 3>(j, M, seed, d_hits, pairs, st)
-                     : entry_census_p<D, 2>(j, M, seed, d_hits, pairs, st);
-#endif
+// f(integral_constant D, integral_constant P) for a job's dof and degree; hipErrorInvalidValue for a
+// pair that has no kernels
+template <class F>
+hipError_t dispatch_dp(int D, int P, F&& f) {
+#define SSPK_DP_CASE(d, p)                                                                               \
+    if constexpr (!kDevOnly || (d == 7 && p == 3)) {                                                     \
+        if (D == d && P == p) return f(std::integral_constant<int, d>{}, std::integral_constant<int, p>{}); \
+    }
+    SSPK_DP_LIST(SSPK_DP_CASE)
+#undef SSPK_DP_CASE
+    return hipErrorInvalidValue;
 }
 
 // The TaskSpacePlanner kernels' selection from the scene: f(og, cbm, up, def) is called once, with
@@ -3146,13 +3185,14 @@ hipError_t entry_tsp_group(const TspK& k, const TspGoals& goals, const sspp_job*
 }
 
 #define SSPK_ENTRY_DECL(X, D, P)                                                                          \
-    X template hipError_t entry_c2f_p<D, P>(const SsppC2F&, const sspp_job*, const SsppPtrs&, int, hipStream_t); \
+    X template hipError_t entry_c2f_p<D, P>(const SsppC2F&, const sspp_job*, const SsppPtrs&, int, hipStream_t, \
+                                            const PairTable&);                                            \
     X template hipError_t entry_census_p<D, P>(const sspp_job*, int, unsigned long long, unsigned long long*,   \
                                                const DPair*, hipStream_t);
 // the query launch's kernels, translation units of their own (sspp_inst.hip with -DSSPK_Q)
 #define SSPK_QENTRY_DECL(X, D, P)                                                                         \
-    X template hipError_t entry_c2f_q_p<D, P>(const SsppC2F&, const sspp_job*, const SsppPtrs&, int, hipStream_t, \
-                                              const SceneT&, const QryPtrs&);
+    X template hipError_t entry_c2f_p<D, P, QryPtrs>(const SsppC2F&, const sspp_job*, const SsppPtrs&, int, \
+                                                     hipStream_t, const PairTable&, const QryPtrs&);
 #define SSPK_TSP_DECL(X)                                                                                  \
     X template hipError_t entry_tsp<0>(const TspK&, const sspp_job*, int, const double*, const double*,    \
                                        const double*, double*, double*, double*, double*, double*, uint8_t*, \

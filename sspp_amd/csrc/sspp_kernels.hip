@@ -1,8 +1,10 @@
 // sspp_kernels.hip — host side of the MI355X scorer: scenes, jobs, launches and the C ABI.
 //
 // The kernels are in sspp_kern.h (their knobs, profiling hooks, LDS layouts and random numbers in
-// sspp_knobs.h, sspp_prof.h, sspp_lds.h, sspp_rng.h); their instantiations are compiled per dof in
-// sspp_inst.hip.
+// sspp_knobs.h, sspp_prof.h, sspp_lds.h, sspp_rng.h) with their launch templates; their
+// instantiations are compiled per (dof, degree) in sspp_inst.hip and reached through dispatch_dp.
+// A job's pair tables are PairTables (sspp_kern.h): this file builds them (set_job_tables,
+// prepass_apply, sspp_job_set_queries) and run_sspp hands a launch the one launch_table picks.
 #include "sspp_kern.h"
 
 #include <chrono>
@@ -12,35 +14,10 @@ using namespace sspk;
 
 #ifndef SSPP_SINGLE_TU
 namespace sspk {
-SSPK_ENTRY_DECL(extern, 1, 2)
-SSPK_ENTRY_DECL(extern, 1, 3)
-SSPK_ENTRY_DECL(extern, 2, 2)
-SSPK_ENTRY_DECL(extern, 2, 3)
-SSPK_ENTRY_DECL(extern, 3, 2)
-SSPK_ENTRY_DECL(extern, 3, 3)
-SSPK_ENTRY_DECL(extern, 4, 2)
-SSPK_ENTRY_DECL(extern, 4, 3)
-SSPK_ENTRY_DECL(extern, 6, 2)
-SSPK_ENTRY_DECL(extern, 6, 3)
-SSPK_ENTRY_DECL(extern, 7, 2)
-SSPK_ENTRY_DECL(extern, 7, 3)
-SSPK_ENTRY_DECL(extern, 9, 2)
-SSPK_ENTRY_DECL(extern, 9, 3)
+#define SSPK_EXTERN_DP(D, P) SSPK_ENTRY_DECL(extern, D, P) SSPK_QENTRY_DECL(extern, D, P)
+SSPK_DP_LIST(SSPK_EXTERN_DP)
+#undef SSPK_EXTERN_DP
 SSPK_TSP_DECL(extern)
-SSPK_QENTRY_DECL(extern, 1, 2)
-SSPK_QENTRY_DECL(extern, 1, 3)
-SSPK_QENTRY_DECL(extern, 2, 2)
-SSPK_QENTRY_DECL(extern, 2, 3)
-SSPK_QENTRY_DECL(extern, 3, 2)
-SSPK_QENTRY_DECL(extern, 3, 3)
-SSPK_QENTRY_DECL(extern, 4, 2)
-SSPK_QENTRY_DECL(extern, 4, 3)
-SSPK_QENTRY_DECL(extern, 6, 2)
-SSPK_QENTRY_DECL(extern, 6, 3)
-SSPK_QENTRY_DECL(extern, 7, 2)
-SSPK_QENTRY_DECL(extern, 7, 3)
-SSPK_QENTRY_DECL(extern, 9, 2)
-SSPK_QENTRY_DECL(extern, 9, 3)
 }  // namespace sspk
 #endif
 
@@ -677,17 +654,6 @@ static std::vector<DPair> reachable_pairs(const sspp_scene* sc, const std::vecto
     return pairs_in_boxes(sc, in, &lo, &hi, 1);
 }
 
-static void table_flags(const sspp_scene* sc, const std::vector<DPair>& t, int* np, int* cb, int* og) {
-    *np = (int)t.size();
-    *cb = 0;
-    *og = 1;
-    for (const DPair& pr : t) {
-        const int tg = sc->geoms[pr.gm].type;
-        *cb |= sspk::table_bits(tg, pr.otype);
-        *og &= pr.gm == t[0].gm;
-    }
-}
-
 // Basis rows for a list of parameters (same A2.1/A2.2 code as the device header).
 // d_tab32 (optional): the same rows rounded to FP32 (k_sspp_c2f's filtered scan)
 static int upload_basis(const std::vector<double>& us, int p, const double* knots, int nknots,
@@ -713,13 +679,11 @@ constexpr int kThroughputNT = 128, kThroughputG1 = 4;
 
 // both pair tables to the device, synchronously (job creation, option changes)
 static int upload_pairs_sync(sspp_job* j) {
-    const sspp_scene* sc = j->scene;
-    const size_t cap = sizeof(DPair) * std::max<size_t>(1, sc->pairs.size());
-    if (!j->d_pairs) HIPCHK(hipMalloc((void**)&j->d_pairs, cap));
-    if (!j->d_pairs_s) HIPCHK(hipMalloc((void**)&j->d_pairs_s, cap));
-    HIPCHK(hipMemcpy(j->d_pairs, j->h_pairs.data(), sizeof(DPair) * j->h_pairs.size(), hipMemcpyHostToDevice));
-    if (!j->h_pairs_s.empty())
-        HIPCHK(hipMemcpy(j->d_pairs_s, j->h_pairs_s.data(), sizeof(DPair) * j->h_pairs_s.size(), hipMemcpyHostToDevice));
+    const size_t cap = sizeof(DPair) * std::max<size_t>(1, j->scene->pairs.size());
+    for (PairTable* t : {&j->tab[kPairsFull], &j->tab[kPairsSampled]}) {
+        if (!t->d) HIPCHK(hipMalloc((void**)&t->d, cap));
+        if (!t->h.empty()) HIPCHK(hipMemcpy(t->d, t->h.data(), sizeof(DPair) * t->h.size(), hipMemcpyHostToDevice));
+    }
     return SSPP_OK;
 }
 
@@ -727,18 +691,9 @@ static int upload_pairs_sync(sspp_job* j) {
 // stream st; pairs: the sampled table to scan (nullptr: the job's)
 static hipError_t launch_census_d(sspp_job* j, int M, unsigned long long* d, const DPair* pairs, hipStream_t st) {
     const unsigned long long seed = j->seed ^ 0xC3A5C85C97CB3127ull;  // independent of the job's candidates
-    switch (j->D) {
-#ifndef SSPP_DEV_ONLY
-        case 1: return entry_census<1>(j, M, seed, d, pairs, st);
-        case 2: return entry_census<2>(j, M, seed, d, pairs, st);
-        case 3: return entry_census<3>(j, M, seed, d, pairs, st);
-        case 4: return entry_census<4>(j, M, seed, d, pairs, st);
-        case 6: return entry_census<6>(j, M, seed, d, pairs, st);
-        case 9: return entry_census<9>(j, M, seed, d, pairs, st);
-#endif
-        case 7: return entry_census<7>(j, M, seed, d, pairs, st);
-    }
-    return hipErrorInvalidValue;
+    return dispatch_dp(j->D, j->p, [&](auto dof, auto deg) {
+        return entry_census_p<decltype(dof)::value, decltype(deg)::value>(j, M, seed, d, pairs, st);
+    });
 }
 
 // the census, synchronously: hit bits to the host
@@ -768,12 +723,11 @@ static int set_job_tables(sspp_job* j, const double* init_ctrl, double sigma, co
                           bool create, void* stream, size_t pin_off = 0) {
     const sspp_scene* sc = j->scene;
     std::vector<int> wps = c2f_order(j->W);
+    PairTable &full = j->tab[kPairsFull], &samp = j->tab[kPairsSampled];
     if (sc && !sc->pairs.empty()) {
-        j->h_pairs = order == 0 ? sc->pairs : pairs_for_job(sc, j->h_knots.data(), j->nknots, j->p, init_ctrl, j->D);
-        j->h_pairs_s = reachable_pairs(sc, j->h_pairs, init_ctrl, j->n, j->D, j->p, sigma, limits, j->sampler);
-        table_flags(sc, j->h_pairs, &j->np_full, &j->cb_full, &j->og_full);
-        table_flags(sc, j->h_pairs_s, &j->np_samp, &j->cb_samp, &j->og_samp);
-        if (order == 2 && create && !j->h_pairs_s.empty() && j->W + 1 <= kCensusMaxPts) {
+        table_set(full, sc, order == 0 ? sc->pairs : pairs_for_job(sc, j->h_knots.data(), j->nknots, j->p, init_ctrl, j->D));
+        table_set(samp, sc, reachable_pairs(sc, full.h, init_ctrl, j->n, j->D, j->p, sigma, limits, j->sampler));
+        if (order == 2 && create && !samp.h.empty() && j->W + 1 <= kCensusMaxPts) {
             // the census scans the sampled table in gap order; then both orders, and the
             // sampled table again (reachable_pairs keeps the order it is given)
             const auto t0 = std::chrono::steady_clock::now();
@@ -783,11 +737,9 @@ static int set_job_tables(sspp_job* j, const double* init_ctrl, double sigma, co
             if ((rc = run_census(j, kCensus, hits))) return rc;
             waypoints_from_census(hits, kCensus, j->W, kThroughputG1, wps);
             const std::vector<int> pick(wps.begin(), wps.begin() + std::min<size_t>(wps.size(), kThroughputG1));
-            pairs_by_hits(sc, j->h_pairs, j->h_knots.data(), j->nknots, j->p, init_ctrl, j->D, sigma, limits, j->W,
-                          pick);
-            j->h_pairs_s = reachable_pairs(sc, j->h_pairs, init_ctrl, j->n, j->D, j->p, sigma, limits, j->sampler);
-            table_flags(sc, j->h_pairs, &j->np_full, &j->cb_full, &j->og_full);
-            table_flags(sc, j->h_pairs_s, &j->np_samp, &j->cb_samp, &j->og_samp);
+            pairs_by_hits(sc, full.h, j->h_knots.data(), j->nknots, j->p, init_ctrl, j->D, sigma, limits, j->W, pick);
+            table_set(full, sc, std::move(full.h));  // (reordered in place)
+            table_set(samp, sc, reachable_pairs(sc, full.h, init_ctrl, j->n, j->D, j->p, sigma, limits, j->sampler));
             j->prepass_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         }
     }
@@ -805,15 +757,15 @@ static int set_job_tables(sspp_job* j, const double* init_ctrl, double sigma, co
         if (rc) return rc;
     }
     if (!sc || sc->pairs.empty()) return SSPP_OK;
-    const size_t bytes = sizeof(DPair) * j->h_pairs.size(), bytes_s = sizeof(DPair) * j->h_pairs_s.size();
+    const size_t bytes = sizeof(DPair) * full.h.size(), bytes_s = sizeof(DPair) * samp.h.size();
     if (create) return upload_pairs_sync(j);
     if (pin_off + bytes + bytes_s > j->h_pin_bytes) return sspp::set_error(SSPP_E_NOMEM, "pair staging too small");
     hipStream_t st = (hipStream_t)stream;
     unsigned char* pa = j->h_pin + pin_off;
-    std::memcpy(pa, j->h_pairs.data(), bytes);
-    std::memcpy(pa + bytes, j->h_pairs_s.data(), bytes_s);
-    HIPCHK(hipMemcpyAsync(j->d_pairs, pa, bytes, hipMemcpyHostToDevice, st));
-    if (bytes_s) HIPCHK(hipMemcpyAsync(j->d_pairs_s, pa + bytes, bytes_s, hipMemcpyHostToDevice, st));
+    std::memcpy(pa, full.h.data(), bytes);
+    std::memcpy(pa + bytes, samp.h.data(), bytes_s);
+    HIPCHK(hipMemcpyAsync(full.d, pa, bytes, hipMemcpyHostToDevice, st));
+    if (bytes_s) HIPCHK(hipMemcpyAsync(samp.d, pa + bytes, bytes_s, hipMemcpyHostToDevice, st));
     return SSPP_OK;
 }
 
@@ -822,37 +774,14 @@ static size_t c2f_lds(const sspp_job* j, int cpb, int nrd) {
     return (size_t)c2f_layout(j->n, j->D, cpb, nrd, j->nm < 1 ? 1 : j->nm, lanes_for(j->W - 1)).bytes;
 }
 
-// The FP32 filter's certified margin for a pair table (sspp_filter.h): FP32's error
-// on a separation grows with the pair's extent (centre distance and box extents are bounded by
-// the two bounding radii plus the margin for every pair that passes the sphere test), about 6e-5 m
-// per metre of extent; eps = 2e-4 m per metre, at least 2e-4.  0 (filter off) past 64 pairs or
-// for pairs larger than 8 m, where the certified range would not be worth it.
-constexpr double kF32EpsPerMetre = 2e-4;
-constexpr float kF32PosLimit = 8.0f;
-static double f32_eps(const sspp_scene* sc, const std::vector<DPair>& t) {
-    if (!sc || t.empty() || t.size() > 64) return 0.0;
-    double S = 1.0;
-    for (const DPair& pr : t) {
-        const DGeom& G = sc->geoms[pr.gm];
-        // the moving geom's offset from its mover's root scales the FP32 pose error like an extent
-        double gofs = 0.0, far = 0.0;
-        for (int k = 0; k < 3; ++k) gofs += G.pos[k] * G.pos[k];
-        gofs = std::sqrt(gofs);
-        const double ext = G.rbound + pr.orbound + pr.margin + gofs;
-        for (int k = 0; k < 3; ++k) far = std::max(far, std::fabs(pr.opos[k]));
-        if (!(ext <= 8.0) || !(far <= 2.0 * kF32PosLimit) || G.rbound <= 0.0) return 0.0;
-        S = std::max(S, ext);
-    }
-    return kF32EpsPerMetre * S;
-}
-
 // The asynchronous pre-pass (sspp::job_create_sspp_async): the census on the job's own stream
 // (scanning its own copy of the sampled table), its hit bits into pinned memory, then a host
 // thread orders the waypoints and pairs exactly as the synchronous creation does.  The thread
 // touches only its copies and the job's pre_* result fields, published by prepass_state = 2.
 static int prepass_start(sspp_job* j, const double* init_ctrl, double sigma, const double* limits) {
     const sspp_scene* sc = j->scene;
-    if (!sc || j->h_pairs_s.empty() || j->W + 1 > kCensusMaxPts) return SSPP_OK;
+    const PairTable& samp = j->tab[kPairsSampled];
+    if (!sc || samp.h.empty() || j->W + 1 > kCensusMaxPts) return SSPP_OK;
     const auto t0 = std::chrono::steady_clock::now();
     const int M = kCensus, nw = (j->W + 64) >> 6;
     const size_t nh = (size_t)M * nw;
@@ -861,8 +790,8 @@ static int prepass_start(sspp_job* j, const double* init_ctrl, double sigma, con
     HIPCHK(hipEventCreateWithFlags(&j->pre_ev, hipEventDisableTiming));
     HIPCHK(hipMalloc((void**)&j->d_hits, sizeof(unsigned long long) * nh));
     HIPCHK(hipHostMalloc((void**)&j->h_hits, sizeof(unsigned long long) * nh, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&j->d_census_pairs, sizeof(DPair) * j->h_pairs_s.size()));
-    HIPCHK(hipMemcpy(j->d_census_pairs, j->h_pairs_s.data(), sizeof(DPair) * j->h_pairs_s.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMalloc((void**)&j->d_census_pairs, sizeof(DPair) * samp.h.size()));
+    HIPCHK(hipMemcpy(j->d_census_pairs, samp.h.data(), sizeof(DPair) * samp.h.size(), hipMemcpyHostToDevice));
     hipError_t e = launch_census_d(j, M, j->d_hits, j->d_census_pairs, j->pre_stream);
     if (e == hipSuccess) e = hipMemcpyAsync(j->h_hits, j->d_hits, sizeof(unsigned long long) * nh, hipMemcpyDeviceToHost, j->pre_stream);
     if (e == hipSuccess) e = hipEventRecord(j->pre_ev, j->pre_stream);
@@ -874,7 +803,7 @@ static int prepass_start(sspp_job* j, const double* init_ctrl, double sigma, con
         int gen;
     };
     Copies c{j->h_knots, std::vector<double>(init_ctrl, init_ctrl + (size_t)j->n * j->D),
-             std::vector<double>(limits, limits + j->D), j->h_pairs, sigma, j->tables_gen};
+             std::vector<double>(limits, limits + j->D), j->tab[kPairsFull].h, sigma, j->tables_gen};
     j->prepass_state.store(1, std::memory_order_relaxed);
     j->prepass_thread = std::thread([j, sc, c = std::move(c), t0, nh]() mutable {
         if (hipEventSynchronize(j->pre_ev) != hipSuccess) {
@@ -887,8 +816,9 @@ static int prepass_start(sspp_job* j, const double* init_ctrl, double sigma, con
         const std::vector<int> pick(wps.begin(), wps.begin() + std::min<size_t>(wps.size(), kThroughputG1));
         pairs_by_hits(sc, c.pairs, c.knots.data(), j->nknots, j->p, c.init.data(), j->D, c.sigma, c.limits.data(), j->W,
                       pick);
-        j->pre_pairs_s = reachable_pairs(sc, c.pairs, c.init.data(), j->n, j->D, j->p, c.sigma, c.limits.data(), j->sampler);
-        j->pre_pairs = std::move(c.pairs);
+        table_set(j->pre[kPairsSampled], sc,
+                  reachable_pairs(sc, c.pairs, c.init.data(), j->n, j->D, j->p, c.sigma, c.limits.data(), j->sampler));
+        table_set(j->pre[kPairsFull], sc, std::move(c.pairs));
         j->pre_wps = std::move(wps);
         j->pre_gen = c.gen;
         j->pre_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -921,21 +851,20 @@ static void prepass_apply(sspp_job* j) {
     }
     if (j->pre_gen == j->tables_gen && j->scene) {
         const size_t cap = sizeof(DPair) * std::max<size_t>(1, j->scene->pairs.size());
-        DPair *dp = nullptr, *dps = nullptr;
-        if (hipMalloc((void**)&dp, cap) == hipSuccess && hipMalloc((void**)&dps, cap) == hipSuccess &&
-            hipMemcpy(dp, j->pre_pairs.data(), sizeof(DPair) * j->pre_pairs.size(), hipMemcpyHostToDevice) == hipSuccess &&
-            (j->pre_pairs_s.empty() ||
-             hipMemcpy(dps, j->pre_pairs_s.data(), sizeof(DPair) * j->pre_pairs_s.size(), hipMemcpyHostToDevice) == hipSuccess)) {
-            j->retired.insert(j->retired.end(), {(void*)j->d_pairs, (void*)j->d_pairs_s});
-            j->d_pairs = dp; j->d_pairs_s = dps;
-            j->h_pairs = j->pre_pairs; j->h_pairs_s = j->pre_pairs_s;
-            table_flags(j->scene, j->h_pairs, &j->np_full, &j->cb_full, &j->og_full);
-            table_flags(j->scene, j->h_pairs_s, &j->np_samp, &j->cb_samp, &j->og_samp);
-            j->pair_order = 2;
-        } else {
-            if (dp) (void)hipFree(dp);
-            if (dps) (void)hipFree(dps);
+        bool ok = true;
+        for (PairTable& t : j->pre)
+            ok = ok && hipMalloc((void**)&t.d, cap) == hipSuccess &&
+                 (t.h.empty() || hipMemcpy(t.d, t.h.data(), sizeof(DPair) * t.h.size(), hipMemcpyHostToDevice) == hipSuccess);
+        for (int i = 0; i < 2; ++i) {
+            if (ok) {  // (the pre-pass's tables keep their flags and FP32 margin: table_set, in the thread)
+                j->retired.push_back(j->tab[i].d);
+                j->tab[i] = j->pre[i];
+            } else if (j->pre[i].d) {
+                (void)hipFree(j->pre[i].d);
+            }
+            j->pre[i].d = nullptr;
         }
+        if (ok) j->pair_order = 2;
     }
     j->prepass_ms = j->pre_ms;
 }
@@ -965,7 +894,7 @@ static int job_create_sspp_impl(const sspp_scene* scene, const sspp_sspp_args* a
     if (!a || !out || !a->knots || !a->init_ctrl || !a->limits)
         return sspp::set_error(SSPP_E_INVAL, "sspp_job_create_sspp: null argument");
     const int D = a->dof, p = a->degree, n = a->n_ctrl, W = a->check_points;
-    if (!(D == 1 || D == 2 || D == 3 || D == 4 || D == 6 || D == 7 || D == 9))
+    if (!dof_supported(D))
         return sspp::set_error(SSPP_E_UNSUPPORTED, "dof must be one of 1,2,3,4,6,7,9");
     if (p < 2 || p > 3) return sspp::set_error(SSPP_E_UNSUPPORTED, "GPU scorer supports spline degree 2 or 3");
     if (n < p + 1) return sspp::set_error(SSPP_E_INVAL, "need at least degree + 1 control points");
@@ -1119,8 +1048,8 @@ static int run_sspp(sspp_job* j, const double* d_ctrl, int64_t first_id, int64_t
         j->part_cap = (int64_t)nblk * steps;
     }
     SsppC2F c{};
-    c.sc = kscene_job(j, d_ctrl == nullptr);
-    if (queries && j->d_pairs_q) { c.sc.npairs = j->np_q; c.sc.onegeom = j->og_q; c.sc.cylbox = j->cb_q; }
+    const PairTable& t = launch_table(j, d_ctrl != nullptr, queries);
+    c.sc = kscene_job(j, t);
     c.has_scene = j->scene != nullptr && (c.sc.npairs > 0 || c.sc.static_block);
     c.sampler = j->sampler;
     c.p = p; c.n = n; c.W = j->W; c.sigma = j->sigma; c.seed = j->seed;
@@ -1133,8 +1062,7 @@ static int run_sspp(sspp_job* j, const double* d_ctrl, int64_t first_id, int64_t
     c.r0 = r0; c.r1 = r1;
     c.nt = nt; c.lds = (int)lds;
     c.ctrl_feas = j->ctrl_feas;
-    const double feps = !(j->f32 && c.has_scene) ? 0.0
-                        : queries ? j->feps_q : f32_eps(j->scene, d_ctrl ? j->h_pairs : j->h_pairs_s);
+    const double feps = j->f32 && c.has_scene ? t.feps : 0.0;
     c.f32 = feps > 0.0 ? 1 : 0;
     c.feps = (float)feps;
     c.fplim = kF32PosLimit;
@@ -1170,42 +1098,17 @@ static int run_sspp(sspp_job* j, const double* d_ctrl, int64_t first_id, int64_t
     }
     SsppPtrs o{d_ctrl, d_ctrl_out, d_arc, d_feasible, d_best, q, &split_used};
     const int nb = nblk * steps;
-    hipError_t e = hipErrorInvalidValue;
     j->last_queries = queries ? steps : 0;
-    if (queries) {
-        const size_t nd = (size_t)n * D, Q = (size_t)steps;
-        const double* qt = (const double*)j->d_qtab;
-        const QryPtrs qq{qt, qt + Q * nd, qt + Q * (nd + D), j->d_qtab + Q * (nd + D + 1)};
-        SceneT T = scene_t(j->scene);
-        if (j->d_pairs_q) { T.pairs = j->d_pairs_q; T.visit = nullptr; }
-        switch (j->D) {
-#ifndef SSPP_DEV_ONLY
-            case 1: e = entry_c2f_q<1>(c, j, o, nb, st, T, qq); break;
-            case 2: e = entry_c2f_q<2>(c, j, o, nb, st, T, qq); break;
-            case 3: e = entry_c2f_q<3>(c, j, o, nb, st, T, qq); break;
-            case 4: e = entry_c2f_q<4>(c, j, o, nb, st, T, qq); break;
-            case 6: e = entry_c2f_q<6>(c, j, o, nb, st, T, qq); break;
-            case 9: e = entry_c2f_q<9>(c, j, o, nb, st, T, qq); break;
-#endif
-            case 7: e = entry_c2f_q<7>(c, j, o, nb, st, T, qq); break;
-        }
-        j->last_split = 0;
-        if (e != hipSuccess) return hip_fail(e, "k_sspp_c2f query launch");
-        return SSPP_OK;
-    }
-    switch (j->D) {
-#ifndef SSPP_DEV_ONLY
-        case 1: e = entry_c2f<1>(c, j, o, nb, st); break;
-        case 2: e = entry_c2f<2>(c, j, o, nb, st); break;
-        case 3: e = entry_c2f<3>(c, j, o, nb, st); break;
-        case 4: e = entry_c2f<4>(c, j, o, nb, st); break;
-        case 6: e = entry_c2f<6>(c, j, o, nb, st); break;
-        case 9: e = entry_c2f<9>(c, j, o, nb, st); break;
-#endif
-        case 7: e = entry_c2f<7>(c, j, o, nb, st); break;
-    }
+    const size_t nd = (size_t)n * D, Q = (size_t)steps;
+    const double* qt = (const double*)j->d_qtab;  // (the set's block: a query launch's QryPtrs)
+    const hipError_t e = dispatch_dp(j->D, j->p, [&](auto dof, auto deg) {
+        constexpr int DV = decltype(dof)::value, PV = decltype(deg)::value;
+        if (!queries) return entry_c2f_p<DV, PV>(c, j, o, nb, st, t);
+        return entry_c2f_p<DV, PV>(c, j, o, nb, st, t,
+                                   QryPtrs{qt, qt + Q * nd, qt + Q * (nd + D), j->d_qtab + Q * (nd + D + 1)});
+    });
     j->last_split = split_used;
-    if (e != hipSuccess) return hip_fail(e, "k_sspp_c2f launch");
+    if (e != hipSuccess) return hip_fail(e, queries ? "k_sspp_c2f query launch" : "k_sspp_c2f launch");
     return SSPP_OK;
 }
 
@@ -1234,7 +1137,7 @@ extern "C" int sspp_job_update_sspp(sspp_job* j, const double* init_ctrl, double
         std::memcmp(j->h_stage.data(), init_ctrl, sizeof(double) * nd) == 0 &&
         std::memcmp(j->h_stage.data() + nd, limits, sizeof(double) * j->D) == 0)
         return SSPP_OK;
-    const bool pairs = j->d_pairs && j->scene;
+    const bool pairs = j->tab[kPairsFull].d && j->scene;
     const size_t vbytes = sizeof(double) * (nd + j->D);
     const size_t need = vbytes + (pairs ? 2 * sizeof(DPair) * j->scene->pairs.size() : 0);
     // the pinned staging is the source of the previous update's copies until they complete
@@ -1290,7 +1193,7 @@ extern "C" int sspp_job_set_queries(sspp_job* j, int Q, const double* init_ctrl,
     }
     if (!j->d_qtab) {  // once per job, sized for kMaxSteps queries
         HIPCHK(hipMalloc((void**)&j->d_qtab, vcap));
-        if (pairs) HIPCHK(hipMalloc((void**)&j->d_pairs_q, pcap));
+        if (pairs) HIPCHK(hipMalloc((void**)&j->tab[kPairsQueries].d, pcap));
         HIPCHK(hipHostMalloc((void**)&j->h_qpin, vcap + pcap, hipHostMallocDefault));
         HIPCHK(hipEventCreateWithFlags(&j->q_ev, hipEventDisableTiming));
     }
@@ -1301,20 +1204,20 @@ extern "C" int sspp_job_set_queries(sspp_job* j, int Q, const double* init_ctrl,
     std::memcpy(hv + Q * (nd + D), sigma, sizeof(double) * Q);
     std::memcpy(hv + Q * (nd + D + 1), seed, sizeof(uint64_t) * Q);
     HIPCHK(hipMemcpyAsync(j->d_qtab, hv, sizeof(double) * nv, hipMemcpyHostToDevice, st));
-    j->np_q = 0; j->cb_q = 0; j->og_q = 1; j->feps_q = 0.0;
-    j->h_pairs_q.clear();
+    PairTable& tq = j->tab[kPairsQueries];
+    std::vector<DPair> reach;
     if (pairs) {
         std::vector<ReachBox> lo((size_t)Q), hi((size_t)Q);
         for (int q = 0; q < Q; ++q)
             reach_box(sc, init_ctrl + q * nd, j->n, j->D, j->p, sigma[q], limits + q * D, j->sampler, lo[q].v, hi[q].v);
-        j->h_pairs_q = pairs_in_boxes(sc, j->h_pairs.empty() ? sc->pairs : j->h_pairs, lo.data(), hi.data(), Q);
-        table_flags(sc, j->h_pairs_q, &j->np_q, &j->cb_q, &j->og_q);
-        j->feps_q = f32_eps(sc, j->h_pairs_q);
-        if (!j->h_pairs_q.empty()) {
-            unsigned char* pp = j->h_qpin + vcap;
-            std::memcpy(pp, j->h_pairs_q.data(), sizeof(DPair) * j->h_pairs_q.size());
-            HIPCHK(hipMemcpyAsync(j->d_pairs_q, pp, sizeof(DPair) * j->h_pairs_q.size(), hipMemcpyHostToDevice, st));
-        }
+        const std::vector<DPair>& full = j->tab[kPairsFull].h;
+        reach = pairs_in_boxes(sc, full.empty() ? sc->pairs : full, lo.data(), hi.data(), Q);
+    }
+    table_set(tq, sc, std::move(reach));
+    if (!tq.h.empty()) {
+        unsigned char* pp = j->h_qpin + vcap;
+        std::memcpy(pp, tq.h.data(), sizeof(DPair) * tq.h.size());
+        HIPCHK(hipMemcpyAsync(tq.d, pp, sizeof(DPair) * tq.h.size(), hipMemcpyHostToDevice, st));
     }
     HIPCHK(hipEventRecord(j->q_ev, st));
     j->q_pending = true;
@@ -1413,10 +1316,10 @@ extern "C" int sspp_job_get_option(const sspp_job* j, int key, int64_t* value) {
         case SSPP_OPT_WP_ORDER: *value = j->wp_order; return SSPP_OK;
         case SSPP_OPT_PREPASS_US: *value = (int64_t)(j->prepass_ms * 1e3); return SSPP_OK;
         // the sampled-candidate table built last: the job's own, or a query set's
-        case SSPP_OPT_NPAIRS: *value = j->view_q ? j->np_q : j->np_samp; return SSPP_OK;
-        case SSPP_OPT_CYLBOX: *value = ((j->view_q ? j->cb_q : j->cb_samp) & sspk::kTableCylBox) != 0; return SSPP_OK;
-        case SSPP_OPT_CAPSULE: *value = ((j->view_q ? j->cb_q : j->cb_samp) & sspk::kTableCapsule) != 0; return SSPP_OK;
-        case SSPP_OPT_CYLCYL: *value = ((j->view_q ? j->cb_q : j->cb_samp) & sspk::kTableCylCyl) != 0; return SSPP_OK;
+        case SSPP_OPT_NPAIRS: *value = launch_table(j, false, j->view_q).np; return SSPP_OK;
+        case SSPP_OPT_CYLBOX: *value = (launch_table(j, false, j->view_q).cb & sspk::kTableCylBox) != 0; return SSPP_OK;
+        case SSPP_OPT_CAPSULE: *value = (launch_table(j, false, j->view_q).cb & sspk::kTableCapsule) != 0; return SSPP_OK;
+        case SSPP_OPT_CYLCYL: *value = (launch_table(j, false, j->view_q).cb & sspk::kTableCylCyl) != 0; return SSPP_OK;
         case SSPP_OPT_F32: *value = j->f32; return SSPP_OK;
         case SSPP_OPT_LAST_F32: *value = j->last_f32; return SSPP_OK;
         case SSPP_OPT_CREATE_US: *value = (int64_t)(j->create_ms * 1e3); return SSPP_OK;
@@ -1725,8 +1628,7 @@ extern "C" void sspp_job_free(sspp_job* j) {
     if (j->d_span) (void)hipFree(j->d_span);
     if (j->d_otab) (void)hipFree(j->d_otab);
     if (j->d_otab32) (void)hipFree(j->d_otab32);
-    if (j->d_pairs) (void)hipFree(j->d_pairs);
-    if (j->d_pairs_s) (void)hipFree(j->d_pairs_s);
+    for (const PairTable& t : j->tab) if (t.d) (void)hipFree(t.d);
     if (j->d_ospan) (void)hipFree(j->d_ospan);
     if (j->d_part) (void)hipFree(j->d_part);
     if (j->d_sync) (void)hipFree(j->d_sync);
@@ -1742,7 +1644,6 @@ extern "C" void sspp_job_free(sspp_job* j) {
         (void)hipEventDestroy(j->q_ev);
     }
     if (j->d_qtab) (void)hipFree(j->d_qtab);
-    if (j->d_pairs_q) (void)hipFree(j->d_pairs_q);
     if (j->h_qpin) (void)hipHostFree(j->h_qpin);
     delete j;
 }
