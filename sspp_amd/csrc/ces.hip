@@ -26,10 +26,12 @@
 #include <cstdlib>
 #include <cmath>
 #include <cstring>
-#include <string>
 #include <vector>
 
 #include "model.h"
+#include "sspp_own.h"
+
+using namespace sspo;
 
 namespace {
 
@@ -539,10 +541,6 @@ __global__ __launch_bounds__(256) void k_ces_stage(int n, int KD, int cap, const
     }
 }
 
-int hip_err(hipError_t e, const char* what) {
-    return sspp::set_error(SSPP_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
 }  // namespace
 
 struct sspp_ces {
@@ -552,22 +550,22 @@ struct sspp_ces {
     long long iter = 0;  // completed evaluations: Philox ids of iteration t start at t * samples
     double lo[4], hi[4];
     double start[4] = {0, 0, 0, 0}, end[4] = {0, 0, 0, 0};
-    CesHdr* d_hdr = nullptr;
-    double *d_mean = nullptr, *d_sigma = nullptr, *d_lbest = nullptr, *d_fixed = nullptr;
-    double *d_L = nullptr, *d_Cnf = nullptr, *d_Cwf = nullptr, *d_cost = nullptr, *d_vias = nullptr;
-    unsigned char* d_status = nullptr;
-    int* d_elite = nullptr;
-    int* d_rank = nullptr;     // [n_slots] rank of each success in the (cost, slot) order
-    int* d_by_rank = nullptr;  // [n_slots] slot of rank r
-    int* d_nsucc = nullptr;
-    double *d_LT = nullptr, *d_LH = nullptr;
+    Dev<CesHdr> d_hdr;
+    Dev<double> d_mean, d_sigma, d_lbest, d_fixed;
+    Dev<double> d_L, d_Cnf, d_Cwf, d_cost, d_vias;
+    Dev<unsigned char> d_status;
+    Dev<int> d_elite;
+    Dev<int> d_rank;     // [n_slots] rank of each success in the (cost, slot) order
+    Dev<int> d_by_rank;  // [n_slots] slot of rank r
+    Dev<int> d_nsucc;
+    Dev<double> d_LT, d_LH;
     hipStream_t last = nullptr;         // stream of the last enqueued operation (sspp_ces_read waits on it)
     bool mixed = false;                 // operations since the last read used more than one stream
     bool any_op = false;
-    unsigned char* h_stage = nullptr;   // pinned: k_ces_stage's output
-    size_t stage_bytes = 0;
+    Pinned<unsigned char> h_stage;      // k_ces_stage's output
     long long staged_iter = -1;         // iteration whose results k_ces_update already staged
     int fused = 1;                      // SSPP_OPT_CES_FUSED (sspp_ces_set_option)
+    ~sspp_ces() { if (job) sspp_job_free(job); }
 };
 
 // every enqueuing entry point notes its stream: sspp_ces_read waits on the last one, or on the
@@ -601,18 +599,7 @@ int sspp_ces_set_option(sspp_ces* p, int key, int64_t value) {
     return sspp::set_error(SSPP_E_INVAL, "unknown option");
 }
 
-void sspp_ces_free(sspp_ces* p) {
-    if (!p) return;
-    if (p->job) sspp_job_free(p->job);
-    for (void* q : {(void*)p->d_hdr, (void*)p->d_mean, (void*)p->d_sigma, (void*)p->d_lbest,
-                    (void*)p->d_fixed, (void*)p->d_L, (void*)p->d_Cnf, (void*)p->d_Cwf,
-                    (void*)p->d_cost, (void*)p->d_vias, (void*)p->d_status, (void*)p->d_elite,
-                    (void*)p->d_LT, (void*)p->d_LH, (void*)p->d_rank, (void*)p->d_by_rank,
-                    (void*)p->d_nsucc})
-        if (q) (void)hipFree(q);
-    if (p->h_stage) (void)hipHostFree(p->h_stage);
-    delete p;
-}
+void sspp_ces_free(sspp_ces* p) { delete p; }
 
 int sspp_ces_create(const sspp_scene* scene, const sspp_ces_config* cfg, int world, sspp_ces** out) {
     sspp::clear_error();
@@ -653,38 +640,17 @@ int sspp_ces_create(const sspp_scene* scene, const sspp_ces_config* cfg, int wor
         LT[m] = m ? std::log((double)m) : 0.0;            // log(i + 1.0), i = m - 1
         LH[m] = std::log((double)m + 0.5);                // log(k + 0.5)
     }
-    hipError_t e;
-    if ((e = hipMalloc((void**)&p->d_hdr, sizeof(CesHdr))) != hipSuccess ||
-        (e = hipMalloc((void**)&p->d_mean, sizeof(double) * kd)) != hipSuccess ||
-        (e = hipMalloc((void**)&p->d_sigma, sizeof(double) * kd)) != hipSuccess ||
-        (e = hipMalloc((void**)&p->d_lbest, sizeof(double) * kd)) != hipSuccess ||
-        (e = hipMalloc((void**)&p->d_fixed, sizeof(double) * 2 * kd)) != hipSuccess ||
-        (e = hipMalloc((void**)&p->d_L, sizeof(double) * ns)) != hipSuccess ||
-        (e = hipMalloc((void**)&p->d_Cnf, sizeof(double) * ns)) != hipSuccess ||
-        (e = hipMalloc((void**)&p->d_Cwf, sizeof(double) * ns)) != hipSuccess ||
-        (e = hipMalloc((void**)&p->d_cost, sizeof(double) * ns)) != hipSuccess ||
-        (e = hipMalloc((void**)&p->d_vias, sizeof(double) * ns * kd)) != hipSuccess ||
-        (e = hipMalloc((void**)&p->d_status, ns)) != hipSuccess ||
-        (e = hipMalloc((void**)&p->d_elite, sizeof(int) * cap)) != hipSuccess ||
-        (e = hipMalloc((void**)&p->d_rank, sizeof(int) * ns)) != hipSuccess ||
-        (e = hipMalloc((void**)&p->d_by_rank, sizeof(int) * ns)) != hipSuccess ||
-        (e = hipMalloc((void**)&p->d_nsucc, sizeof(int))) != hipSuccess ||
-        (e = hipMalloc((void**)&p->d_LT, sizeof(double) * LT.size())) != hipSuccess ||
-        (e = hipMalloc((void**)&p->d_LH, sizeof(double) * LH.size())) != hipSuccess ||
-        (e = hipMemcpy(p->d_LT, LT.data(), sizeof(double) * LT.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(p->d_LH, LH.data(), sizeof(double) * LH.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemset(p->d_hdr, 0, sizeof(CesHdr))) != hipSuccess ||
-        (e = hipMemset(p->d_lbest, 0, sizeof(double) * kd)) != hipSuccess ||
-        (e = hipMemset(p->d_mean, 0, sizeof(double) * kd)) != hipSuccess ||
-        (e = hipMemset(p->d_sigma, 0, sizeof(double) * kd)) != hipSuccess ||
-        (e = hipMemset(p->d_status, 0, ns)) != hipSuccess ||
-        (e = hipMemset(p->d_rank, 0, sizeof(int) * ns)) != hipSuccess ||
-        (e = hipMemset(p->d_by_rank, 0, sizeof(int) * ns)) != hipSuccess ||
-        (e = hipMemset(p->d_nsucc, 0, sizeof(int))) != hipSuccess ||
-        (p->stage_bytes = kStageHdr + sizeof(double) * (4 * ns + ns * kd + 3 * kd) + sizeof(int) * (size_t)cap + ns,
-         (e = hipHostMalloc((void**)&p->h_stage, p->stage_bytes, hipHostMallocDefault)) != hipSuccess)) {
-        rc = hip_err(e, "sspp_ces_create allocation");
-        sspp_ces_free(p);
+    const size_t stage_bytes = kStageHdr + sizeof(double) * (4 * ns + ns * kd + 3 * kd) + sizeof(int) * (size_t)cap + ns;
+    if ((rc = p->d_hdr.reserve(1)) || (rc = p->d_mean.reserve(kd)) || (rc = p->d_sigma.reserve(kd)) ||
+        (rc = p->d_lbest.reserve(kd)) || (rc = p->d_fixed.reserve(2 * kd)) || (rc = p->d_L.reserve(ns)) ||
+        (rc = p->d_Cnf.reserve(ns)) || (rc = p->d_Cwf.reserve(ns)) || (rc = p->d_cost.reserve(ns)) ||
+        (rc = p->d_vias.reserve(ns * kd)) || (rc = p->d_status.reserve(ns)) || (rc = p->d_elite.reserve((size_t)cap)) ||
+        (rc = p->d_rank.reserve(ns)) || (rc = p->d_by_rank.reserve(ns)) || (rc = p->d_nsucc.reserve(1)) ||
+        (rc = p->d_LT.upload(LT.data(), LT.size())) || (rc = p->d_LH.upload(LH.data(), LH.size())) ||
+        (rc = p->d_hdr.zero()) || (rc = p->d_lbest.zero()) || (rc = p->d_mean.zero()) || (rc = p->d_sigma.zero()) ||
+        (rc = p->d_status.zero()) || (rc = p->d_rank.zero()) || (rc = p->d_by_rank.zero()) || (rc = p->d_nsucc.zero()) ||
+        (rc = p->h_stage.reserve(stage_bytes))) {
+        delete p;
         return rc;
     }
     *out = p;
@@ -730,18 +696,16 @@ int sspp_ces_begin(sspp_ces* p, const double* start, const double* end, int iter
     note_stream(p, (hipStream_t)stream);
     p->staged_iter = -1;
     hipLaunchKernelGGL(k_ces_begin, dim3(1), dim3(128), 0, (hipStream_t)stream, ces_k(p), iterate ? 1 : 0,
-                       r, p->d_hdr, p->d_mean, p->d_sigma, p->d_lbest, p->d_fixed);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_err(e, "k_ces_begin launch");
-    return SSPP_OK;
+                       r, p->d_hdr.p, p->d_mean.p, p->d_sigma.p, p->d_lbest.p, p->d_fixed.p);
+    return hip_fail(hipGetLastError(), "k_ces_begin launch");
 }
 
 int sspp_ces_eval(sspp_ces* p, int rank, void* stream) {
     sspp::clear_error();
     if (!p || rank < 0 || rank >= p->world) return sspp::set_error(SSPP_E_INVAL, "sspp_ces_eval: bad rank");
     sspp::TspCesEval ev{};
-    ev.fixed = p->d_fixed; ev.nfixed = &p->d_hdr->nfixed;
-    ev.mean = p->d_mean; ev.sigma = p->d_sigma;
+    ev.fixed = p->d_fixed.p; ev.nfixed = &p->d_hdr.p->nfixed;
+    ev.mean = p->d_mean.p; ev.sigma = p->d_sigma.p;
     ev.slot0 = (long long)rank * p->spr;
     ev.samples = p->cfg.samples;
     ev.first_id = p->iter * (long long)p->cfg.samples;
@@ -749,8 +713,8 @@ int sspp_ces_eval(sspp_ces* p, int rank, void* stream) {
     const size_t o = (size_t)rank * p->spr;
     note_stream(p, (hipStream_t)stream);
     p->staged_iter = -1;
-    return sspp::tsp_eval_ces(p->job, &ev, p->spr, p->d_L + o, p->d_Cnf + o, p->d_Cwf + o,
-                              p->d_status + o, p->d_cost + o, p->d_vias + o * 4 * p->K, stream);
+    return sspp::tsp_eval_ces(p->job, &ev, p->spr, p->d_L.p + o, p->d_Cnf.p + o, p->d_Cwf.p + o,
+                              p->d_status.p + o, p->d_cost.p + o, p->d_vias.p + o * 4 * p->K, stream);
 }
 
 int sspp_ces_update(sspp_ces* p, void* stream) {
@@ -761,18 +725,18 @@ int sspp_ces_update(sspp_ces* p, void* stream) {
     note_stream(p, st);
     const int fused = p->nslots <= kCesThreads && p->fused;
     if (!fused) {
-        hipLaunchKernelGGL(k_ces_rank, dim3(nt, nt), dim3(kRankTile), 0, st, p->nslots, p->d_cost,
-                           p->d_status, p->d_rank, p->d_nsucc);
-        hipLaunchKernelGGL(k_ces_scatter, dim3(nt), dim3(256), 0, st, p->nslots, p->d_cost, p->d_status,
-                           p->d_rank, p->d_by_rank);
+        hipLaunchKernelGGL(k_ces_rank, dim3(nt, nt), dim3(kRankTile), 0, st, p->nslots, p->d_cost.p,
+                           p->d_status.p, p->d_rank.p, p->d_nsucc.p);
+        hipLaunchKernelGGL(k_ces_scatter, dim3(nt), dim3(256), 0, st, p->nslots, p->d_cost.p, p->d_status.p,
+                           p->d_rank.p, p->d_by_rank.p);
     }
     // small lists: the update also fills sspp_ces_read's pinned staging (no staging launch)
-    unsigned char* stage = fused ? p->h_stage : nullptr;
-    hipLaunchKernelGGL(k_ces_update, dim3(1), dim3(kCesThreads), 0, st, ces_k(p), fused, p->d_status,
-                       p->d_cost, p->d_by_rank, p->d_nsucc, p->d_vias, p->d_LT, p->d_LH, p->d_hdr, p->d_mean,
-                       p->d_sigma, p->d_lbest, p->d_elite, p->d_L, p->d_Cnf, p->d_Cwf, stage);
+    unsigned char* stage = fused ? p->h_stage.p : nullptr;
+    hipLaunchKernelGGL(k_ces_update, dim3(1), dim3(kCesThreads), 0, st, ces_k(p), fused, p->d_status.p,
+                       p->d_cost.p, p->d_by_rank.p, p->d_nsucc.p, p->d_vias.p, p->d_LT.p, p->d_LH.p, p->d_hdr.p, p->d_mean.p,
+                       p->d_sigma.p, p->d_lbest.p, p->d_elite.p, p->d_L.p, p->d_Cnf.p, p->d_Cwf.p, stage);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_err(e, "k_ces_update launch");
+    if (e != hipSuccess) return hip_fail(e, "k_ces_update launch");
     p->iter++;
     p->staged_iter = stage ? p->iter : -1;
     return SSPP_OK;
@@ -837,19 +801,19 @@ int sspp_ces_plan_group(sspp_ces* const* ps, int G, const double* starts, const 
     for (int g = 0; g < G; ++g) {
         sspp_ces* p = ps[g];
         CesGoalDev& q = gd.g[g];
-        q.h = p->d_hdr; q.mean = p->d_mean; q.sigma = p->d_sigma; q.lbest = p->d_lbest; q.fixed = p->d_fixed;
-        q.status = p->d_status; q.cost = p->d_cost; q.vias = p->d_vias; q.L = p->d_L; q.Cnf = p->d_Cnf;
-        q.Cwf = p->d_Cwf; q.rank = p->d_rank; q.by_rank = p->d_by_rank; q.nsucc = p->d_nsucc; q.elite = p->d_elite;
+        q.h = p->d_hdr.p; q.mean = p->d_mean.p; q.sigma = p->d_sigma.p; q.lbest = p->d_lbest.p; q.fixed = p->d_fixed.p;
+        q.status = p->d_status.p; q.cost = p->d_cost.p; q.vias = p->d_vias.p; q.L = p->d_L.p; q.Cnf = p->d_Cnf.p;
+        q.Cwf = p->d_Cwf.p; q.rank = p->d_rank.p; q.by_rank = p->d_by_rank.p; q.nsucc = p->d_nsucc.p; q.elite = p->d_elite.p;
         for (int i = 0; i < 4; ++i) {
             q.start[i] = p->start[i] = starts[4 * g + i];
             q.end[i] = p->end[i] = ends[4 * g + i];
         }
         jobs[g] = p->job;
         sspp::TspCesEval& e = evs[g];
-        e.fixed = p->d_fixed; e.nfixed = &p->d_hdr->nfixed; e.mean = p->d_mean; e.sigma = p->d_sigma;
+        e.fixed = p->d_fixed.p; e.nfixed = &p->d_hdr.p->nfixed; e.mean = p->d_mean.p; e.sigma = p->d_sigma.p;
         e.slot0 = 0; e.samples = p->cfg.samples;
         for (int i = 0; i < 4; ++i) { e.start[i] = p->start[i]; e.end[i] = p->end[i]; }
-        outs[g] = sspp::TspCesOut{p->d_L, p->d_Cnf, p->d_Cwf, p->d_cost, p->d_vias, p->d_status};
+        outs[g] = sspp::TspCesOut{p->d_L.p, p->d_Cnf.p, p->d_Cwf.p, p->d_cost.p, p->d_vias.p, p->d_status.p};
     }
     const int n = p0->nslots;
     const int fused = n <= kCesThreads && p0->fused;
@@ -860,12 +824,12 @@ int sspp_ces_plan_group(sspp_ces* const* ps, int G, const double* starts, const 
             note_stream(p, st);
             p->staged_iter = -1;
             evs[g].first_id = p->iter * (long long)p->cfg.samples;
-            gd.g[g].stage = fused ? p->h_stage : nullptr;
+            gd.g[g].stage = fused ? p->h_stage.p : nullptr;
         }
         hipLaunchKernelGGL(k_ces_begin_group, dim3(1, 1, G), dim3(128), 0, st, c0, (t > 0 || iterate) ? 1 : 0,
                            p0->cfg.total_points, s0, gd);
         hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_err(e, "k_ces_begin_group launch");
+        if (e != hipSuccess) return hip_fail(e, "k_ces_begin_group launch");
         int rc = sspp::tsp_eval_ces_group(jobs.data(), evs.data(), outs.data(), G, n, stream);
         if (rc == SSPP_E_UNSUPPORTED && t == 0) {
             // the evaluation cannot be batched: this iteration's begin ran for every goal, so
@@ -883,10 +847,10 @@ int sspp_ces_plan_group(sspp_ces* const* ps, int G, const double* starts, const 
             hipLaunchKernelGGL(k_ces_rank_group, dim3(nt, nt, G), dim3(kRankTile), 0, st, n, gd);
             hipLaunchKernelGGL(k_ces_scatter_group, dim3(nt, 1, G), dim3(256), 0, st, n, gd);
         }
-        hipLaunchKernelGGL(k_ces_update_group, dim3(1, 1, G), dim3(kCesThreads), 0, st, c0, fused, p0->d_LT,
-                           p0->d_LH, gd);
+        hipLaunchKernelGGL(k_ces_update_group, dim3(1, 1, G), dim3(kCesThreads), 0, st, c0, fused, p0->d_LT.p,
+                           p0->d_LH.p, gd);
         e = hipGetLastError();
-        if (e != hipSuccess) return hip_err(e, "k_ces_update_group launch");
+        if (e != hipSuccess) return hip_fail(e, "k_ces_update_group launch");
         for (int g = 0; g < G; ++g) {
             ps[g]->iter++;
             ps[g]->staged_iter = fused ? ps[g]->iter : -1;
@@ -902,10 +866,9 @@ int sspp_ces_pack(const sspp_ces* p, int rank, double* d_out, void* stream) {
     const int KD = 4 * p->K;
     const long long tot = (long long)p->spr * (5 + KD);
     const int g = (int)std::min<long long>((tot + 255) / 256, 1024);
-    hipLaunchKernelGGL(k_ces_pack, dim3(g), dim3(256), 0, (hipStream_t)stream, p->spr, KD, p->d_L + o,
-                       p->d_Cnf + o, p->d_Cwf + o, p->d_cost + o, p->d_status + o, p->d_vias + o * KD, d_out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SSPP_OK : hip_err(e, "k_ces_pack launch");
+    hipLaunchKernelGGL(k_ces_pack, dim3(g), dim3(256), 0, (hipStream_t)stream, p->spr, KD, p->d_L.p + o,
+                       p->d_Cnf.p + o, p->d_Cwf.p + o, p->d_cost.p + o, p->d_status.p + o, p->d_vias.p + o * KD, d_out);
+    return hip_fail(hipGetLastError(), "k_ces_pack launch");
 }
 
 int sspp_ces_unpack(sspp_ces* p, const double* d_in, void* stream) {
@@ -917,17 +880,16 @@ int sspp_ces_unpack(sspp_ces* p, const double* d_in, void* stream) {
     note_stream(p, (hipStream_t)stream);
     p->staged_iter = -1;
     hipLaunchKernelGGL(k_ces_unpack, dim3(g), dim3(256), 0, (hipStream_t)stream, p->nslots, KD, d_in,
-                       p->d_L, p->d_Cnf, p->d_Cwf, p->d_cost, p->d_status, p->d_vias);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? SSPP_OK : hip_err(e, "k_ces_unpack launch");
+                       p->d_L.p, p->d_Cnf.p, p->d_Cwf.p, p->d_cost.p, p->d_status.p, p->d_vias.p);
+    return hip_fail(hipGetLastError(), "k_ces_unpack launch");
 }
 
 int sspp_ces_get_buffers(const sspp_ces* p, sspp_ces_buffers* out) {
     if (!p || !out) return sspp::set_error(SSPP_E_INVAL, "sspp_ces_get_buffers: null argument");
-    out->L = p->d_L; out->C_nf = p->d_Cnf; out->C_wf = p->d_Cwf; out->cost = p->d_cost;
-    out->status = p->d_status; out->vias = p->d_vias;
-    out->mean = p->d_mean; out->sigma = p->d_sigma; out->last_best = p->d_lbest;
-    out->elites = p->d_elite;
+    out->L = p->d_L.p; out->C_nf = p->d_Cnf.p; out->C_wf = p->d_Cwf.p; out->cost = p->d_cost.p;
+    out->status = p->d_status.p; out->vias = p->d_vias.p;
+    out->mean = p->d_mean.p; out->sigma = p->d_sigma.p; out->last_best = p->d_lbest.p;
+    out->elites = p->d_elite.p;
     return SSPP_OK;
 }
 
@@ -944,26 +906,26 @@ int sspp_ces_read(sspp_ces* p, sspp_ces_state* st, double* L, double* Cnf, doubl
     hipError_t e = hipSuccess;
     if (p->mixed) {
         e = hipDeviceSynchronize();
-        if (e != hipSuccess) return hip_err(e, "sspp_ces_read");
+        if (e != hipSuccess) return hip_fail(e, "sspp_ces_read");
         p->mixed = false;
     }
     if (p->staged_iter != p->iter) {
         const long long tot = 4LL * n + (long long)n * KD + 3LL * KD + p->cap + n;
         const int g = (int)std::min<long long>((tot + 255) / 256, 256);
-        hipLaunchKernelGGL(k_ces_stage, dim3(g), dim3(256), 0, p->last, n, KD, p->cap, p->d_hdr, p->d_L,
-                           p->d_Cnf, p->d_Cwf, p->d_cost, p->d_vias, p->d_mean, p->d_sigma, p->d_lbest,
-                           p->d_elite, p->d_status, p->h_stage);
+        hipLaunchKernelGGL(k_ces_stage, dim3(g), dim3(256), 0, p->last, n, KD, p->cap, p->d_hdr.p, p->d_L.p,
+                           p->d_Cnf.p, p->d_Cwf.p, p->d_cost.p, p->d_vias.p, p->d_mean.p, p->d_sigma.p, p->d_lbest.p,
+                           p->d_elite.p, p->d_status.p, p->h_stage.p);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(p->last);
-    if (e != hipSuccess) return hip_err(e, "sspp_ces_read");
+    if (e != hipSuccess) return hip_fail(e, "sspp_ces_read");
     // everything enqueued so far has completed: the next operation starts a new record, so a
     // read's stream differing from the next operation's does not count as mixed (which would
     // make the next read wait on the whole device, other planners' streams included)
     p->any_op = false;
     p->mixed = false;
     CesHdr h;
-    std::memcpy(&h, p->h_stage, sizeof h);
+    std::memcpy(&h, p->h_stage.p, sizeof h);
     st->n_fixed = h.nfixed;
     st->n_candidates = h.nfixed + p->cfg.samples;
     st->n_success = h.nsucc;
@@ -973,7 +935,7 @@ int sspp_ces_read(sspp_ces* p, sspp_ces_state* st, double* L, double* Cnf, doubl
     st->best_cost = h.best_cost;
     st->iteration = p->iter;
     const size_t m = (size_t)st->n_candidates, kd = (size_t)KD;
-    const double* sd = (const double*)(p->h_stage + kStageHdr);
+    const double* sd = (const double*)(p->h_stage.p + kStageHdr);
     const size_t ov = 4 * (size_t)n, om = ov + (size_t)n * kd, oe = om + 3 * kd;
     const int32_t* si = (const int32_t*)(sd + oe);
     const uint8_t* sb = (const uint8_t*)(si + p->cap);
@@ -994,15 +956,15 @@ int sspp_ces_set_state(sspp_ces* p, const double* mean, const double* sigma, con
     p->staged_iter = -1;  // the staged copy no longer matches the device state
     const size_t kd = (size_t)4 * p->K;
     hipError_t e;
-    if ((mean && (e = hipMemcpy(p->d_mean, mean, 8 * kd, hipMemcpyHostToDevice)) != hipSuccess) ||
-        (sigma && (e = hipMemcpy(p->d_sigma, sigma, 8 * kd, hipMemcpyHostToDevice)) != hipSuccess) ||
-        (last_best && (e = hipMemcpy(p->d_lbest, last_best, 8 * kd, hipMemcpyHostToDevice)) != hipSuccess))
-        return hip_err(e, "sspp_ces_set_state copy");
+    if ((mean && (e = hipMemcpy(p->d_mean.p, mean, 8 * kd, hipMemcpyHostToDevice)) != hipSuccess) ||
+        (sigma && (e = hipMemcpy(p->d_sigma.p, sigma, 8 * kd, hipMemcpyHostToDevice)) != hipSuccess) ||
+        (last_best && (e = hipMemcpy(p->d_lbest.p, last_best, 8 * kd, hipMemcpyHostToDevice)) != hipSuccess))
+        return hip_fail(e, "sspp_ces_set_state copy");
     if (has_best >= 0) {
         CesHdr h;
-        if ((e = hipMemcpy(&h, p->d_hdr, sizeof h, hipMemcpyDeviceToHost)) != hipSuccess ||
-            (h.has_best = has_best, (e = hipMemcpy(p->d_hdr, &h, sizeof h, hipMemcpyHostToDevice)) != hipSuccess))
-            return hip_err(e, "sspp_ces_set_state header");
+        if ((e = hipMemcpy(&h, p->d_hdr.p, sizeof h, hipMemcpyDeviceToHost)) != hipSuccess ||
+            (h.has_best = has_best, (e = hipMemcpy(p->d_hdr.p, &h, sizeof h, hipMemcpyHostToDevice)) != hipSuccess))
+            return hip_fail(e, "sspp_ces_set_state header");
     }
     return SSPP_OK;
 }

@@ -18,58 +18,17 @@
 #include <algorithm>
 #include <cstring>
 #include <mutex>
-#include <string>
 #include <vector>
 
 #include "model.h"
+#include "sspp_own.h"
+
+using namespace sspo;
 
 namespace {
 
-int hipck(hipError_t e, const char* what) {
-    if (e == hipSuccess) return SSPP_OK;
-    return sspp::set_error(SSPP_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-template <class T>
-struct Dev {
-    T* p = nullptr;
-    size_t n = 0;
-    ~Dev() { if (p) (void)hipFree(p); }
-    int reserve(size_t count) {
-        if (count <= n) return SSPP_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr; n = 0;
-        hipError_t e = hipMalloc((void**)&p, sizeof(T) * (count ? count : 1));
-        if (e != hipSuccess) return sspp::set_error(SSPP_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-        n = count;
-        return SSPP_OK;
-    }
-};
-
-template <class T>
-struct Pinned {
-    T* p = nullptr;
-    T* d = nullptr;  // its device address (mapped), looked up once per allocation
-    size_t n = 0;
-    ~Pinned() { if (p) (void)hipHostFree(p); }
-    int reserve(size_t count) {
-        if (count <= n) return SSPP_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; d = nullptr; n = 0;
-        hipError_t e = hipHostMalloc((void**)&p, sizeof(T) * (count ? count : 1),
-                                     hipHostMallocMapped | hipHostMallocCoherent);
-        if (e != hipSuccess) return sspp::set_error(SSPP_E_NOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-        n = count;
-        return SSPP_OK;
-    }
-    T* dev() {
-        if (!d && p) {
-            void* q = nullptr;
-            if (hipHostGetDevicePointer(&q, p, 0) == hipSuccess) d = (T*)q;
-        }
-        return d;
-    }
-};
+// the scoring kernel writes into the planner's pinned buffers: mapped, coherent
+constexpr unsigned kMapped = hipHostMallocMapped | hipHostMallocCoherent;
 
 struct JobRef {
     sspp_job* j = nullptr;
@@ -90,18 +49,18 @@ struct sspp_planner {
     Dev<double> d_arc, d_ctrl;
     Dev<unsigned char> d_feas;
     Dev<sspp_best> d_best;
-    Pinned<double> h_arc, h_ctrl;      // plan(): the scoring kernel's outputs (mapped)
-    Pinned<unsigned char> h_feas;
-    Pinned<sspp_best> h_best;
+    Pinned<double> h_arc{kMapped}, h_ctrl{kMapped};  // plan(): the scoring kernel's outputs
+    Pinned<unsigned char> h_feas{kMapped};
+    Pinned<sspp_best> h_best{kMapped};
     // score(): job keyed on (knots, n, W, collision)
     JobRef score_job;
     std::vector<double> score_knots;
     int score_W = 0, score_coll = -1;
     int64_t score_cap = 0;
-    Pinned<double> h_in;
-    Pinned<double> h_sarc;
-    Pinned<unsigned char> h_sfeas;
-    Pinned<sspp_best> h_sbest;
+    Pinned<double> h_in{kMapped};
+    Pinned<double> h_sarc{kMapped};
+    Pinned<unsigned char> h_sfeas{kMapped};
+    Pinned<sspp_best> h_sbest{kMapped};
     Dev<double> d_in;
     // plan_many(): a job of its own per shape (the plan() job and buffers stay as they are),
     // device outputs of one chunk of queries, pinned results of the whole call
@@ -111,9 +70,9 @@ struct sspp_planner {
     Dev<double> dm_arc, dm_ctrl;
     Dev<unsigned char> dm_feas;
     Dev<sspp_best> dm_best;
-    Pinned<sspp_best> hm_best;
-    Pinned<double> hm_ctrl, hm_arc;
-    Pinned<unsigned char> hm_feas;
+    Pinned<sspp_best> hm_best{kMapped};
+    Pinned<double> hm_ctrl{kMapped}, hm_arc{kMapped};
+    Pinned<unsigned char> hm_feas{kMapped};
     ~sspp_planner() {
         if (stream) (void)hipStreamSynchronize(stream);  // this planner's work on the shared stream
         plan_job.reset();
@@ -226,7 +185,7 @@ extern "C" int sspp_planner_plan(sspp_planner* p, const double* start, const dou
     int rc;
     if ((rc = plan_enqueue(p, start, end, sigma, limits, sample_count, check_points, init_points, seed,
                            first_id, knots_out, true)) ||
-        (rc = hipck(hipStreamSynchronize(p->stream), "plan")))
+        (rc = hip_fail(hipStreamSynchronize(p->stream), "plan")))
         return rc;
     // the feasible candidates in candidate order (findBestPath's input, include/sspp.h:215-216)
     // and findBestPath itself (include/sspp.h:171-192): a path is taken when its arc length is
@@ -326,15 +285,15 @@ extern "C" int sspp_planner_plan_many(sspp_planner* p, int Q, const double* star
             return rc;
         hipLaunchKernelGGL(k_gather_best, dim3(qc), dim3(64), 0, p->stream, p->dm_best.p, p->dm_ctrl.p, (long long)first_id,
                            (long long)B, (int)nd, hb + q0, hc + (size_t)q0 * nd);
-        if ((rc = hipck(hipGetLastError(), "k_gather_best"))) return rc;
-        if (arc_out && (rc = hipck(hipMemcpyAsync(p->hm_arc.p + (size_t)q0 * B, p->dm_arc.p, sizeof(double) * qc * B,
+        if ((rc = hip_fail(hipGetLastError(), "k_gather_best"))) return rc;
+        if (arc_out && (rc = hip_fail(hipMemcpyAsync(p->hm_arc.p + (size_t)q0 * B, p->dm_arc.p, sizeof(double) * qc * B,
                                                   hipMemcpyDeviceToHost, p->stream), "copy arc")))
             return rc;
-        if (feasible_out && (rc = hipck(hipMemcpyAsync(p->hm_feas.p + (size_t)q0 * B, p->dm_feas.p, (size_t)qc * B,
+        if (feasible_out && (rc = hip_fail(hipMemcpyAsync(p->hm_feas.p + (size_t)q0 * B, p->dm_feas.p, (size_t)qc * B,
                                                        hipMemcpyDeviceToHost, p->stream), "copy feasible")))
             return rc;
     }
-    if ((rc = hipck(hipStreamSynchronize(p->stream), "plan_many"))) return rc;
+    if ((rc = hip_fail(hipStreamSynchronize(p->stream), "plan_many"))) return rc;
     if ((rc = sspp_best_check(p->hm_best.p, Q))) return rc;
     std::memcpy(best_out, p->hm_best.p, sizeof(sspp_best) * Q);
     std::memcpy(best_ctrl_out, p->hm_ctrl.p, sizeof(double) * Q * nd);
@@ -397,12 +356,12 @@ extern "C" int sspp_plan_sspp(const sspp_scene* scene, int dof, const double* st
     const size_t nd = (size_t)init_points * dof;
     if ((rc = p->h_sarc.reserve(B)) || (rc = p->h_sfeas.reserve(B)) || (rc = p->h_sbest.reserve(1)))
         return rc;
-    if ((rc = hipck(hipMemcpyAsync(p->h_sarc.p, p->d_arc.p, sizeof(double) * B, hipMemcpyDeviceToHost, p->stream), "copy arc")) ||
-        (rc = hipck(hipMemcpyAsync(p->h_sfeas.p, p->d_feas.p, (size_t)B, hipMemcpyDeviceToHost, p->stream), "copy feasible")) ||
-        (rc = hipck(hipMemcpyAsync(p->h_sbest.p, p->d_best.p, sizeof(sspp_best), hipMemcpyDeviceToHost, p->stream), "copy best")) ||
-        (ctrl_out && (rc = hipck(hipMemcpyAsync(p->h_ctrl.p, p->d_ctrl.p, sizeof(double) * B * nd,
+    if ((rc = hip_fail(hipMemcpyAsync(p->h_sarc.p, p->d_arc.p, sizeof(double) * B, hipMemcpyDeviceToHost, p->stream), "copy arc")) ||
+        (rc = hip_fail(hipMemcpyAsync(p->h_sfeas.p, p->d_feas.p, (size_t)B, hipMemcpyDeviceToHost, p->stream), "copy feasible")) ||
+        (rc = hip_fail(hipMemcpyAsync(p->h_sbest.p, p->d_best.p, sizeof(sspp_best), hipMemcpyDeviceToHost, p->stream), "copy best")) ||
+        (ctrl_out && (rc = hip_fail(hipMemcpyAsync(p->h_ctrl.p, p->d_ctrl.p, sizeof(double) * B * nd,
                                                 hipMemcpyDeviceToHost, p->stream), "copy ctrl"))) ||
-        (rc = hipck(hipStreamSynchronize(p->stream), "plan")))
+        (rc = hip_fail(hipStreamSynchronize(p->stream), "plan")))
         return rc;
     std::memcpy(arc_out, p->h_sarc.p, sizeof(double) * B);
     std::memcpy(feasible_out, p->h_sfeas.p, (size_t)B);
@@ -442,16 +401,16 @@ extern "C" int sspp_planner_score(sspp_planner* p, const double* knots, int degr
         }
     }
     std::memcpy(p->h_in.p, ctrl, sizeof(double) * B * nd);
-    if ((rc = hipck(hipMemcpyAsync(p->d_in.p, p->h_in.p, sizeof(double) * B * nd, hipMemcpyHostToDevice,
+    if ((rc = hip_fail(hipMemcpyAsync(p->d_in.p, p->h_in.p, sizeof(double) * B * nd, hipMemcpyHostToDevice,
                                    p->stream), "copy splines")))
         return rc;
     if ((rc = sspp_job_score_ctrl(p->score_job.j, p->d_in.p, 0, B, p->d_arc.p, p->d_feas.p, p->d_best.p,
                                   p->stream)))
         return rc;
-    if ((rc = hipck(hipMemcpyAsync(p->h_sarc.p, p->d_arc.p, sizeof(double) * B, hipMemcpyDeviceToHost, p->stream), "copy arc")) ||
-        (rc = hipck(hipMemcpyAsync(p->h_sfeas.p, p->d_feas.p, (size_t)B, hipMemcpyDeviceToHost, p->stream), "copy feasible")) ||
-        (rc = hipck(hipMemcpyAsync(p->h_sbest.p, p->d_best.p, sizeof(sspp_best), hipMemcpyDeviceToHost, p->stream), "copy best")) ||
-        (rc = hipck(hipStreamSynchronize(p->stream), "score")))
+    if ((rc = hip_fail(hipMemcpyAsync(p->h_sarc.p, p->d_arc.p, sizeof(double) * B, hipMemcpyDeviceToHost, p->stream), "copy arc")) ||
+        (rc = hip_fail(hipMemcpyAsync(p->h_sfeas.p, p->d_feas.p, (size_t)B, hipMemcpyDeviceToHost, p->stream), "copy feasible")) ||
+        (rc = hip_fail(hipMemcpyAsync(p->h_sbest.p, p->d_best.p, sizeof(sspp_best), hipMemcpyDeviceToHost, p->stream), "copy best")) ||
+        (rc = hip_fail(hipStreamSynchronize(p->stream), "score")))
         return rc;
     if (arc_out) std::memcpy(arc_out, p->h_sarc.p, sizeof(double) * B);
     if (feasible_out) std::memcpy(feasible_out, p->h_sfeas.p, (size_t)B);

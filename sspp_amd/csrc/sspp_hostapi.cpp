@@ -6,28 +6,14 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
-#include <string>
 #include <vector>
 
 #include "model.h"
+#include "sspp_own.h"
+
+using namespace sspo;
 
 namespace {
-
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) {
-        hipError_t e = hipMalloc(&p, bytes ? bytes : 8);
-        if (e != hipSuccess)
-            return sspp::set_error(SSPP_E_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-        return SSPP_OK;
-    }
-};
-
-int hipck(hipError_t e, const char* what) {
-    if (e == hipSuccess) return SSPP_OK;
-    return sspp::set_error(SSPP_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
 
 struct JobGuard {
     sspp_job* j = nullptr;
@@ -47,33 +33,31 @@ int run_job_host(const sspp_scene* scene, const double* knots, int degree, const
     int rc = sspp_job_create_sspp(scene, &a, B, &jg.j);
     if (rc) return rc;
     const size_t nd = (size_t)n * D;
-    DevBuf d_arc, d_feas, d_best, d_ctrl;
-    if ((rc = d_arc.alloc(sizeof(double) * B)) || (rc = d_feas.alloc((size_t)B)) ||
-        (rc = d_best.alloc(sizeof(sspp_best))))
-        return rc;
+    Dev<double> d_arc, d_ctrl;
+    Dev<uint8_t> d_feas;
+    Dev<sspp_best> d_best;
+    if ((rc = d_arc.reserve((size_t)B)) || (rc = d_feas.reserve((size_t)B)) || (rc = d_best.reserve(1))) return rc;
     if (ctrl_in || ctrl_out) {
-        if ((rc = d_ctrl.alloc(sizeof(double) * nd * B))) return rc;
+        if ((rc = d_ctrl.reserve(nd * B))) return rc;
     }
     if (ctrl_in) {
-        if ((rc = hipck(hipMemcpy(d_ctrl.p, ctrl_in, sizeof(double) * nd * B, hipMemcpyHostToDevice), "copy ctrl")))
+        if ((rc = hip_fail(hipMemcpy(d_ctrl.p, ctrl_in, sizeof(double) * nd * B, hipMemcpyHostToDevice), "copy ctrl")))
             return rc;
-        rc = sspp_job_score_ctrl(jg.j, (const double*)d_ctrl.p, first_id, B, (double*)d_arc.p,
-                                 (uint8_t*)d_feas.p, (sspp_best*)d_best.p, nullptr);
+        rc = sspp_job_score_ctrl(jg.j, d_ctrl.p, first_id, B, d_arc.p, d_feas.p, d_best.p, nullptr);
     } else {
-        rc = sspp_job_sample_score(jg.j, first_id, B, (double*)d_arc.p, (uint8_t*)d_feas.p,
-                                   ctrl_out ? (double*)d_ctrl.p : nullptr, (sspp_best*)d_best.p, nullptr);
+        rc = sspp_job_sample_score(jg.j, first_id, B, d_arc.p, d_feas.p, ctrl_out ? d_ctrl.p : nullptr, d_best.p, nullptr);
     }
     if (rc) return rc;
-    if ((rc = hipck(hipDeviceSynchronize(), "kernel"))) return rc;
-    if (arc_out && (rc = hipck(hipMemcpy(arc_out, d_arc.p, sizeof(double) * B, hipMemcpyDeviceToHost), "copy arc")))
+    if ((rc = hip_fail(hipDeviceSynchronize(), "kernel"))) return rc;
+    if (arc_out && (rc = hip_fail(hipMemcpy(arc_out, d_arc.p, sizeof(double) * B, hipMemcpyDeviceToHost), "copy arc")))
         return rc;
-    if (feasible_out && (rc = hipck(hipMemcpy(feasible_out, d_feas.p, (size_t)B, hipMemcpyDeviceToHost), "copy feasible")))
+    if (feasible_out && (rc = hip_fail(hipMemcpy(feasible_out, d_feas.p, (size_t)B, hipMemcpyDeviceToHost), "copy feasible")))
         return rc;
-    if (best_out && ((rc = hipck(hipMemcpy(best_out, d_best.p, sizeof(sspp_best), hipMemcpyDeviceToHost), "copy best")) ||
+    if (best_out && ((rc = hip_fail(hipMemcpy(best_out, d_best.p, sizeof(sspp_best), hipMemcpyDeviceToHost), "copy best")) ||
                      (rc = sspp_best_check(best_out, 1))))
         return rc;
     if (ctrl_out && !ctrl_in &&
-        (rc = hipck(hipMemcpy(ctrl_out, d_ctrl.p, sizeof(double) * nd * B, hipMemcpyDeviceToHost), "copy ctrl")))
+        (rc = hip_fail(hipMemcpy(ctrl_out, d_ctrl.p, sizeof(double) * nd * B, hipMemcpyDeviceToHost), "copy ctrl")))
         return rc;
     return SSPP_OK;
 }

@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "model.h"
+#include "sspp_own.h"
 #include "sspp_prof.h"
 #include "sspp_knobs.h"
 #include "sspp_lds.h"
@@ -2704,6 +2705,7 @@ inline size_t tsp_base_lds(int cpb, int n, int rep) {
 }  // namespace sspk
 
 using namespace sspk;
+using namespace sspo;
 
 struct sspp_scene {
     int mode, arg, dof;
@@ -2713,19 +2715,20 @@ struct sspp_scene {
     std::vector<DMover> movers;
     int n_moving_geoms = 0, n_static_geoms = 0, n_static_pairs = 0, static_contacts = 0;
     double static_cost = 0.0;
-    DGeom* d_geoms = nullptr;
-    DPair* d_pairs = nullptr;
-    DMover* d_movers = nullptr;
-    DPair* d_visit = nullptr;  // the pairs grouped by moving geom (SceneT::visit)
+    Dev<DGeom> d_geoms;
+    Dev<DPair> d_pairs;  // (null without pairs, as d_visit without a visit order)
+    Dev<DMover> d_movers;
+    Dev<DPair> d_visit;  // the pairs grouped by moving geom (SceneT::visit)
     int device = 0;
 };
 
 // A pair table: the pairs one launch scans, in scan order, on the host and on the device, with what
 // the host derives from them — the kernel selection (KScene's npairs / cylbox / onegeom) and the
 // FP32 filter's margin.  table_set fills all of it but the device copy, which the owner uploads.
+// Move-only: the device copy has one owner.
 struct PairTable {
     std::vector<DPair> h;
-    DPair* d = nullptr;
+    Dev<DPair> d;
     int np = 0, cb = 0, og = 1;  // pairs, table_bits of them all, one moving geom
     double feps = 0.0;           // f32_eps (0: the launch runs without the FP32 filter)
 };
@@ -2786,15 +2789,11 @@ struct sspp_job {
     int64_t max_batch = 0;
     double sigma = 0.0;
     uint64_t seed = 0;
-    double* d_knots = nullptr;
-    double* d_tab = nullptr;   // basis rows (host-precomputed, P+1 doubles per waypoint)
-    int* d_span = nullptr;     // knot span per waypoint
-    double* d_init = nullptr;
-    double* d_limits = nullptr;
-    double* d_Minv = nullptr;
-    double* d_mean = nullptr;
-    double* d_sigma = nullptr;
-    BlockBest* d_part = nullptr;
+    Dev<double> d_knots;
+    Dev<double> d_tab;         // basis rows (host-precomputed, P+1 doubles per waypoint)
+    Dev<int> d_span;           // knot span per waypoint
+    Dev<double> d_init, d_limits, d_Minv, d_mean, d_sigma;
+    Dev<BlockBest> d_part;
     int64_t part_cap = 0;      // BlockBest records d_part holds
     int sampler = 0;           // 0 FP64 Box-Muller pairs (default), 1 FP32 quads (opt-in)
     int arc_all = 0;           // arc length for every candidate (else collision-free only)
@@ -2808,12 +2807,12 @@ struct sspp_job {
     int f32 = 1;               // k_sspp_c2f's FP32-filtered scan (SSPP_OPT_F32; results identical)
     int last_f32 = 0;          // whether the last launch ran it
     double prepass_ms = 0.0;   // host time of the hit-order pre-pass at creation
-    double* d_otab = nullptr;  // collision rows in the job's waypoint order
-    float* d_otab32 = nullptr; // the same rows in FP32 (k_sspp_c2f's filtered scan)
-    int* d_ospan = nullptr;
+    Dev<double> d_otab;        // collision rows in the job's waypoint order
+    Dev<float> d_otab32;       // the same rows in FP32 (k_sspp_c2f's filtered scan)
+    Dev<int> d_ospan;
     std::vector<int> h_wps;    // that order
     PairTable tab[kPairTables];  // this job's pair tables (launch_table picks a launch's)
-    ArgminSync* d_sync = nullptr;  // sharded arrival counters of the fused argmin [kMaxSteps]
+    Dev<ArgminSync> d_sync;        // sharded arrival counters of the fused argmin [kMaxSteps]
     std::vector<double> h_knots;   // host copies: the knot vector, and the values the device
     std::vector<double> h_stage;   // holds (init | limits; sspp_job_update_sspp skips equal updates)
     int ctrl_feas = 0;               // k_sspp_c2f writes ctrl_out rows of feasible candidates only
@@ -2821,14 +2820,12 @@ struct sspp_job {
     // 1 k_tsp_pp, 2 k_tsp_pp2) and the generic (non-upright) narrowphase
     int tsp_form = -1, tsp_generic = 0, last_form = -1;
     int tsp_rep = -1, last_rep = 1;     // SSPP_OPT_TSP_REP
-    unsigned* d_pp_nd = nullptr;     // k_tsp_pp2 records / arrival counters (allocated on first use)
-    double* d_pp_term = nullptr;
-    unsigned* d_pp_arrive = nullptr;
+    Dev<unsigned> d_pp_nd;           // k_tsp_pp2 records / arrival counters (allocated on first use)
+    Dev<double> d_pp_term;
+    Dev<unsigned> d_pp_arrive;
     int64_t pp_cap = 0;
-    unsigned char* h_pin = nullptr;  // pinned source of sspp_job_update_sspp's async copies
-    size_t h_pin_bytes = 0;
-    hipEvent_t upd_ev = nullptr;     // recorded after those copies: the next update waits on it
-    bool upd_pending = false;
+    Staging upd;                     // pinned source of sspp_job_update_sspp's async copies, and the
+                                     // event recorded after them: the next update waits on it
     double start[4], end[4], lo[4], hi[4];
     double z_min = 0, w_col = 1, floor_z_min = 0, floor_margin = 0.01, floor_scale = 10;
     // asynchronous hit-order pre-pass (the drop-in planner's first plan(): DESIGN.md §5): the
@@ -2843,21 +2840,21 @@ struct sspp_job {
     int pre_gen = 0;                    // tables_gen the result was computed for
     int tables_gen = 0;                 // bumped by every update that re-derives the pair tables
     hipStream_t pre_stream = nullptr;
-    hipEvent_t pre_ev = nullptr;
-    unsigned long long* d_hits = nullptr;
-    unsigned long long* h_hits = nullptr;  // pinned
-    DPair* d_census_pairs = nullptr;    // the census's own copy of the sampled table
-    std::vector<void*> retired;         // device tables replaced while kernels may still read them
+    Event pre_ev;
+    Dev<unsigned long long> d_hits;
+    Pinned<unsigned long long> h_hits;
+    Dev<DPair> d_census_pairs;          // the census's own copy of the sampled table
+    Retired retired;                    // device tables replaced while kernels may still read them
     double create_ms = 0.0;             // host time of sspp_job_create_sspp
     // split launches: the survivor queue (SurvQ), grown on demand
     int opt_split = 1;                  // SSPP_OPT_SPLIT
     int last_split = 0;
-    SurvQ* d_sq_hdr = nullptr;
-    unsigned long long* d_sq_rec = nullptr;
-    double* d_sq_ctrl = nullptr;
-    float* d_sq_ctrl32 = nullptr;
-    SurvBest* d_sq_res = nullptr;
-    unsigned* d_sq_orphan = nullptr;
+    Dev<SurvQ> d_sq_hdr;
+    Dev<unsigned long long> d_sq_rec;
+    Dev<double> d_sq_ctrl;
+    Dev<float> d_sq_ctrl32;
+    Dev<SurvBest> d_sq_res;
+    Dev<unsigned> d_sq_orphan;
     int opt_linger_us = 10000;          // SSPP_OPT_SPLIT_LINGER_US (10 ms)
     int opt_split_drop = 0;             // SSPP_OPT_SPLIT_DROP (tests)
     unsigned* dbg_beacon = nullptr;     // SSPP_OPT_DEBUG_BEACONS (-DSSPP_DEBUG_PROGRESS builds)
@@ -2868,12 +2865,21 @@ struct sspp_job {
     // (tab[kPairsQueries]: a pair some query can reach); the single-query state above is not touched
     int nq = 0;                         // queries of the last sspp_job_set_queries (0: none yet)
     int last_queries = 0;               // queries of the last launch (0: an ordinary launch)
-    unsigned long long* d_qtab = nullptr;
+    Dev<unsigned long long> d_qtab;
     int view_q = 0;                     // the job's most recently built sampled table is a set's: the
                                         // get-options that describe "the sampled table" read it
-    unsigned char* h_qpin = nullptr;    // pinned source of the set's async copies
-    hipEvent_t q_ev = nullptr;          // recorded after them: the next set waits on it
-    bool q_pending = false;
+    Staging qst;                        // pinned source of the set's async copies, and the event
+                                        // recorded after them: the next set waits on it
+    // wait for a running pre-pass and drop its result (option changes, the destructor)
+    void prepass_drop() {
+        if (prepass_thread.joinable()) prepass_thread.join();
+        prepass_state.store(3, std::memory_order_relaxed);
+    }
+    // the thread and the pre-pass stream use the members: both are done before any member dies
+    ~sspp_job() {
+        prepass_drop();
+        if (pre_stream) (void)hipStreamSynchronize(pre_stream);
+    }
 };
 
 
@@ -2911,10 +2917,10 @@ inline KScene kscene(const sspp_scene* s, bool tsp, bool generic = false) {
 inline SceneT scene_t(const sspp_scene* s) {
     SceneT t{};
     if (!s) return t;
-    t.geoms = s->d_geoms;
-    t.pairs = s->d_pairs;
-    t.movers = s->d_movers;
-    t.visit = s->d_visit;
+    t.geoms = s->d_geoms.p;
+    t.pairs = s->d_pairs.p;
+    t.movers = s->d_movers.p;
+    t.visit = s->d_visit.p;
     return t;
 }
 
@@ -2937,12 +2943,12 @@ inline const PairTable& launch_table(const sspp_job* j, bool ctrl_in, bool queri
 // without pairs) leaves the scene's own values.
 inline SceneT scene_t_job(const sspp_job* j, const PairTable& t) {
     SceneT s = scene_t(j->scene);
-    if (t.d) { s.pairs = t.d; s.visit = nullptr; }  // (another order)
+    if (t.d.p) { s.pairs = t.d.p; s.visit = nullptr; }  // (another order)
     return s;
 }
 inline KScene kscene_job(const sspp_job* j, const PairTable& t) {
     KScene k = kscene(j->scene, false);
-    if (t.d) { k.npairs = t.np; k.onegeom = t.og; k.cylbox = t.cb; }
+    if (t.d.p) { k.npairs = t.np; k.onegeom = t.og; k.cylbox = t.cb; }
     return k;
 }
 
@@ -2973,10 +2979,10 @@ template <int D, int NM, int P, int NT, class... Q>
 hipError_t launch_c2f_nt(const SsppC2F& k, const sspp_job* j, const SsppPtrs& o, int nblk, hipStream_t st,
                          const PairTable& t, const Q&... qq) {
     constexpr bool QM = sizeof...(Q) != 0;
-    const double* atab = j->d_tab + (size_t)(j->W + 1) * (P + 1);
-    const int* aspan = j->d_span + (j->W + 1);
+    const double* atab = j->d_tab.p + (size_t)(j->W + 1) * (P + 1);
+    const int* aspan = j->d_span.p + (j->W + 1);
     const SceneT T = scene_t_job(j, t);
-    const double *init = j->d_init, *limits = j->d_limits;
+    const double *init = j->d_init.p, *limits = j->d_limits.p;
     if constexpr (QM) [&](const QryPtrs& qt) { init = qt.init; limits = qt.limits; }(qq...);
 #define SSPP_LAUNCH_C2F(NMV, OGV, CBV, SPV)                                                               \
     do {                                                                                                  \
@@ -2984,8 +2990,8 @@ hipError_t launch_c2f_nt(const SsppC2F& k, const sspp_job* j, const SsppPtrs& o,
         kk.split = SPV;                                                                                   \
         if (o.split_used) *o.split_used = SPV;                                                            \
         hipLaunchKernelGGL((k_sspp_c2f<D, NMV, P, OGV, NT, CBV, SPV, QM, Q...>), dim3(nblk), dim3(NT), kk.lds, st, \
-                           kk, T, j->d_otab, j->d_otab32, j->d_ospan, atab, aspan, init, limits, o.ctrl_in, \
-                           o.ctrl_out, o.arc, o.feasible, j->d_part, j->d_sync, o.best, o.q, qq...);     \
+                           kk, T, j->d_otab.p, j->d_otab32.p, j->d_ospan.p, atab, aspan, init, limits, o.ctrl_in, \
+                           o.ctrl_out, o.arc, o.feasible, j->d_part.p, j->d_sync.p, o.best, o.q, qq...);     \
     } while (0)
     const bool og = NM == 1 && k.sc.onegeom && k.sc.npairs > 0;
     if (og && k.sc.cylbox) SSPP_LAUNCH_C2F(1, true, true, false);
@@ -3032,18 +3038,18 @@ hipError_t launch_census(const sspp_job* j, int M, unsigned long long seed, unsi
     if (sc.cylbox & (kTableCapsule | kTableCylCyl)) {  // the instantiations that carry those pairs' colliders
         if (og)
             hipLaunchKernelGGL((k_sspp_census<D, 1, P, true, true>), dim3(M), dim3(kCensusThreads), lds, st, sc, T,
-                               j->n, j->W, j->sampler, j->sigma, seed, j->d_tab, j->d_span, j->d_init, j->d_limits,
+                               j->n, j->W, j->sampler, j->sigma, seed, j->d_tab.p, j->d_span.p, j->d_init.p, j->d_limits.p,
                                d_hits);
         else
             hipLaunchKernelGGL((k_sspp_census<D, NM, P, false, true>), dim3(M), dim3(kCensusThreads), lds, st, sc, T,
-                               j->n, j->W, j->sampler, j->sigma, seed, j->d_tab, j->d_span, j->d_init, j->d_limits,
+                               j->n, j->W, j->sampler, j->sigma, seed, j->d_tab.p, j->d_span.p, j->d_init.p, j->d_limits.p,
                                d_hits);
     } else if (og)
         hipLaunchKernelGGL((k_sspp_census<D, 1, P, true>), dim3(M), dim3(kCensusThreads), lds, st, sc, T, j->n, j->W,
-                           j->sampler, j->sigma, seed, j->d_tab, j->d_span, j->d_init, j->d_limits, d_hits);
+                           j->sampler, j->sigma, seed, j->d_tab.p, j->d_span.p, j->d_init.p, j->d_limits.p, d_hits);
     else
         hipLaunchKernelGGL((k_sspp_census<D, NM, P, false>), dim3(M), dim3(kCensusThreads), lds, st, sc, T, j->n,
-                           j->W, j->sampler, j->sigma, seed, j->d_tab, j->d_span, j->d_init, j->d_limits, d_hits);
+                           j->W, j->sampler, j->sigma, seed, j->d_tab.p, j->d_span.p, j->d_init.p, j->d_limits.p, d_hits);
     return hipGetLastError();
 }
 
@@ -3155,16 +3161,16 @@ hipError_t entry_tsp(const TspK& k, const sspp_job* j, int nblk, const double* m
         constexpr int CBV = decltype(cbm)::value, DEFV = decltype(defc)::value;
         if (pp == 2)
             hipLaunchKernelGGL((k_tsp_pp2<1, OG, CBV, 8>), dim3(nblk), dim3(512), (size_t)tsp_pp_layout(j->n, false).bytes,
-                               st, k, tt, j->d_tab, j->d_span, j->d_Minv, mean, sigma, d_vias, d_vias_out, d_L, d_Cnf,
-                               d_Cwf, d_cost, d_status, j->d_part, j->d_sync, d_best);
+                               st, k, tt, j->d_tab.p, j->d_span.p, j->d_Minv.p, mean, sigma, d_vias, d_vias_out, d_L, d_Cnf,
+                               d_Cwf, d_cost, d_status, j->d_part.p, j->d_sync.p, d_best);
         else if (pp == 1)
             hipLaunchKernelGGL((k_tsp_pp<1, OG, CBV, 8>), dim3(nblk), dim3(512), (size_t)tsp_pp_layout(j->n, true).bytes,
-                               st, k, tt, j->d_tab, j->d_span, j->d_Minv, mean, sigma, d_vias, d_vias_out, d_L, d_Cnf,
-                               d_Cwf, d_cost, d_status, j->d_part, j->d_sync, d_best);
+                               st, k, tt, j->d_tab.p, j->d_span.p, j->d_Minv.p, mean, sigma, d_vias, d_vias_out, d_L, d_Cnf,
+                               d_Cwf, d_cost, d_status, j->d_part.p, j->d_sync.p, d_best);
         else
             hipLaunchKernelGGL((k_tsp<1, OG, CBV, UP, DEFV>), dim3(nblk), dim3(kBlock), tsp_lds(k, j, DEFV), st, k, tt,
-                               j->d_tab, j->d_span, j->d_Minv, mean, sigma, d_vias, d_vias_out, d_L, d_Cnf, d_Cwf,
-                               d_cost, d_status, j->d_part, j->d_sync, d_best);
+                               j->d_tab.p, j->d_span.p, j->d_Minv.p, mean, sigma, d_vias, d_vias_out, d_L, d_Cnf, d_Cwf,
+                               d_cost, d_status, j->d_part.p, j->d_sync.p, d_best);
     });
     return hipGetLastError();
 }
@@ -3178,8 +3184,8 @@ hipError_t entry_tsp_group(const TspK& k, const TspGoals& goals, const sspp_job*
     tsp_dispatch(k.sc, def, [&](auto og, auto cbm, auto up, auto defc) {
         constexpr int DEFV = decltype(defc)::value;
         hipLaunchKernelGGL((k_tsp_group<1, decltype(og)::value, decltype(cbm)::value, decltype(up)::value, DEFV>),
-                           dim3(nblk), dim3(kBlock), tsp_lds(k, j, DEFV), st, k, goals, tt, j->d_tab, j->d_span,
-                           j->d_Minv);
+                           dim3(nblk), dim3(kBlock), tsp_lds(k, j, DEFV), st, k, goals, tt, j->d_tab.p, j->d_span.p,
+                           j->d_Minv.p);
     });
     return hipGetLastError();
 }

@@ -5,6 +5,7 @@
 // instantiations are compiled per (dof, degree) in sspp_inst.hip and reached through dispatch_dp.
 // A job's pair tables are PairTables (sspp_kern.h): this file builds them (set_job_tables,
 // prepass_apply, sspp_job_set_queries) and run_sspp hands a launch the one launch_table picks.
+// Device buffers, pinned memory and events are members of the owning types of sspp_own.h.
 #include "sspp_kern.h"
 
 #include <chrono>
@@ -65,23 +66,6 @@ __global__ __launch_bounds__(kArgminThreads) void k_argmin(const BlockBest* __re
 
 // =============================================================== host side: scene + jobs
 namespace {
-
-int hip_fail(hipError_t e, const char* what) {
-    return sspp::set_error(SSPP_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-#define HIPCHK(x)                                   \
-    do {                                            \
-        hipError_t e_ = (x);                        \
-        if (e_ != hipSuccess) return hip_fail(e_, #x); \
-    } while (0)
-
-template <class T>
-int upload(T** dst, const T* src, size_t count) {
-    if (count == 0) { *dst = nullptr; return SSPP_OK; }
-    HIPCHK(hipMalloc((void**)dst, sizeof(T) * count));
-    HIPCHK(hipMemcpy(*dst, src, sizeof(T) * count, hipMemcpyHostToDevice));
-    return SSPP_OK;
-}
 
 // MuJoCo-like kinematics on the host (same operation order as oracle/sspp_oracle.c::fk)
 void host_fk(const sspp_model& m, const std::vector<double>& qpos, std::vector<double>& xpos,
@@ -312,10 +296,10 @@ int sspp_scene_create(const sspp_model* m, int mode, int arg, int count_static, 
         }
     }
     int rc;
-    if ((rc = upload(&s->d_geoms, s->geoms.data(), s->geoms.size())) ||
-        (rc = upload(&s->d_pairs, s->pairs.data(), s->pairs.size())) ||
-        (rc = upload(&s->d_movers, s->movers.data(), s->movers.size())) ||
-        (rc = upload(&s->d_visit, visit.data(), visit.size()))) {
+    if ((rc = s->d_geoms.upload(s->geoms.data(), s->geoms.size())) ||
+        (rc = s->d_pairs.upload(s->pairs.data(), s->pairs.size())) ||
+        (rc = s->d_movers.upload(s->movers.data(), s->movers.size())) ||
+        (rc = s->d_visit.upload(visit.data(), visit.size()))) {
         sspp_scene_free(s);
         return rc;
     }
@@ -338,10 +322,6 @@ int sspp_scene_get_info(const sspp_scene* s, sspp_scene_info* out) {
 void sspp_scene_free(sspp_scene* s) {
     if (!s) return;
     sspp::planner_cache_drop(s);
-    if (s->d_geoms) (void)hipFree(s->d_geoms);
-    if (s->d_pairs) (void)hipFree(s->d_pairs);
-    if (s->d_movers) (void)hipFree(s->d_movers);
-    if (s->d_visit) (void)hipFree(s->d_visit);
     delete s;
 }
 
@@ -657,34 +637,36 @@ static std::vector<DPair> reachable_pairs(const sspp_scene* sc, const std::vecto
 // Basis rows for a list of parameters (same A2.1/A2.2 code as the device header).
 // d_tab32 (optional): the same rows rounded to FP32 (k_sspp_c2f's filtered scan)
 static int upload_basis(const std::vector<double>& us, int p, const double* knots, int nknots,
-                        double** d_tab, int** d_span, float** d_tab32 = nullptr) {
+                        Dev<double>& d_tab, Dev<int>& d_span, Dev<float>* d_tab32 = nullptr) {
     std::vector<double> tab(us.size() * (p + 1));
     std::vector<int> sp(us.size());
     for (size_t i = 0; i < us.size(); ++i) {
         sp[i] = span_of(us[i], p, knots, nknots);
         basis_funcs(us[i], p, sp[i], knots, &tab[i * (p + 1)]);
     }
-    int rc = upload(d_tab, tab.data(), tab.size());
+    int rc = d_tab.upload(tab.data(), tab.size());
     if (rc) return rc;
     if (d_tab32) {
         std::vector<float> t32(tab.begin(), tab.end());
-        if ((rc = upload(d_tab32, t32.data(), t32.size()))) return rc;
+        if ((rc = d_tab32->upload(t32.data(), t32.size()))) return rc;
     }
-    return upload(d_span, sp.data(), sp.size());
+    return d_span.upload(sp.data(), sp.size());
 }
 
 // the throughput shape: 2-wave workgroups of 32 candidates x 4 phase-1 lanes (DESIGN.md §5:
 // against one-wave workgroups of 16, a survivor's remaining waypoints spread over 128 lanes)
 constexpr int kThroughputNT = 128, kThroughputG1 = 4;
 
+// a table to its device copy, synchronously; the copy has room for every pair of the scene, so that
+// an update's larger table fits it
+static int table_upload(PairTable& t, const sspp_scene* sc) {
+    if (int rc = t.d.reserve(std::max<size_t>(1, sc->pairs.size()))) return rc;
+    return t.d.upload(t.h.data(), t.h.size());
+}
 // both pair tables to the device, synchronously (job creation, option changes)
 static int upload_pairs_sync(sspp_job* j) {
-    const size_t cap = sizeof(DPair) * std::max<size_t>(1, j->scene->pairs.size());
-    for (PairTable* t : {&j->tab[kPairsFull], &j->tab[kPairsSampled]}) {
-        if (!t->d) HIPCHK(hipMalloc((void**)&t->d, cap));
-        if (!t->h.empty()) HIPCHK(hipMemcpy(t->d, t->h.data(), sizeof(DPair) * t->h.size(), hipMemcpyHostToDevice));
-    }
-    return SSPP_OK;
+    if (int rc = table_upload(j->tab[kPairsFull], j->scene)) return rc;
+    return table_upload(j->tab[kPairsSampled], j->scene);
 }
 
 // the hit census (k_sspp_census) of M candidates into d (hit bits [M][ceil((W + 1) / 64)]), on
@@ -699,14 +681,12 @@ static hipError_t launch_census_d(sspp_job* j, int M, unsigned long long* d, con
 // the census, synchronously: hit bits to the host
 static int run_census(sspp_job* j, int M, std::vector<uint64_t>& hits) {
     const int nw = (j->W + 64) >> 6;
-    unsigned long long* d = nullptr;
-    HIPCHK(hipMalloc((void**)&d, sizeof(unsigned long long) * (size_t)M * nw));
-    hipError_t e = launch_census_d(j, M, d, nullptr, nullptr);
+    Dev<unsigned long long> d;
+    if (int rc = d.reserve((size_t)M * nw)) return rc;
+    hipError_t e = launch_census_d(j, M, d.p, nullptr, nullptr);
     hits.assign((size_t)M * nw, 0ull);
-    if (e == hipSuccess) e = hipMemcpy(hits.data(), d, sizeof(uint64_t) * hits.size(), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return hip_fail(e, "k_sspp_census");
-    return SSPP_OK;
+    if (e == hipSuccess) e = hipMemcpy(hits.data(), d.p, sizeof(uint64_t) * hits.size(), hipMemcpyDeviceToHost);
+    return hip_fail(e, "k_sspp_census");
 }
 
 // The census scans every collision waypoint of kCensus candidates: above this many waypoints the
@@ -750,22 +730,19 @@ static int set_job_tables(sspp_job* j, const double* init_ctrl, double sigma, co
         j->h_wps = wps;
         std::vector<double> uo;
         for (int i : wps) uo.push_back((double)i / j->W);
-        if (j->d_otab) { (void)hipFree(j->d_otab); j->d_otab = nullptr; }
-        if (j->d_otab32) { (void)hipFree(j->d_otab32); j->d_otab32 = nullptr; }
-        if (j->d_ospan) { (void)hipFree(j->d_ospan); j->d_ospan = nullptr; }
-        int rc = upload_basis(uo, j->p, j->h_knots.data(), j->nknots, &j->d_otab, &j->d_ospan, &j->d_otab32);
+        int rc = upload_basis(uo, j->p, j->h_knots.data(), j->nknots, j->d_otab, j->d_ospan, &j->d_otab32);
         if (rc) return rc;
     }
     if (!sc || sc->pairs.empty()) return SSPP_OK;
     const size_t bytes = sizeof(DPair) * full.h.size(), bytes_s = sizeof(DPair) * samp.h.size();
     if (create) return upload_pairs_sync(j);
-    if (pin_off + bytes + bytes_s > j->h_pin_bytes) return sspp::set_error(SSPP_E_NOMEM, "pair staging too small");
+    if (pin_off + bytes + bytes_s > j->upd.buf.n) return sspp::set_error(SSPP_E_NOMEM, "pair staging too small");
     hipStream_t st = (hipStream_t)stream;
-    unsigned char* pa = j->h_pin + pin_off;
+    unsigned char* pa = j->upd.buf.p + pin_off;
     std::memcpy(pa, full.h.data(), bytes);
     std::memcpy(pa + bytes, samp.h.data(), bytes_s);
-    HIPCHK(hipMemcpyAsync(full.d, pa, bytes, hipMemcpyHostToDevice, st));
-    if (bytes_s) HIPCHK(hipMemcpyAsync(samp.d, pa + bytes, bytes_s, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(full.d.p, pa, bytes, hipMemcpyHostToDevice, st));
+    if (bytes_s) HIPCHK(hipMemcpyAsync(samp.d.p, pa + bytes, bytes_s, hipMemcpyHostToDevice, st));
     return SSPP_OK;
 }
 
@@ -787,15 +764,15 @@ static int prepass_start(sspp_job* j, const double* init_ctrl, double sigma, con
     const size_t nh = (size_t)M * nw;
     j->pre_stream = (hipStream_t)sspp::shared_stream(1);  // shared by every job's pre-pass, not owned
     if (!j->pre_stream) return sspp::set_error(SSPP_E_HIP, "hipStreamCreate (shared pre-pass stream)");
-    HIPCHK(hipEventCreateWithFlags(&j->pre_ev, hipEventDisableTiming));
-    HIPCHK(hipMalloc((void**)&j->d_hits, sizeof(unsigned long long) * nh));
-    HIPCHK(hipHostMalloc((void**)&j->h_hits, sizeof(unsigned long long) * nh, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&j->d_census_pairs, sizeof(DPair) * samp.h.size()));
-    HIPCHK(hipMemcpy(j->d_census_pairs, samp.h.data(), sizeof(DPair) * samp.h.size(), hipMemcpyHostToDevice));
-    hipError_t e = launch_census_d(j, M, j->d_hits, j->d_census_pairs, j->pre_stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(j->h_hits, j->d_hits, sizeof(unsigned long long) * nh, hipMemcpyDeviceToHost, j->pre_stream);
-    if (e == hipSuccess) e = hipEventRecord(j->pre_ev, j->pre_stream);
-    if (e != hipSuccess) return hip_fail(e, "k_sspp_census (asynchronous pre-pass)");
+    int rc;
+    if ((rc = j->pre_ev.ensure()) || (rc = j->d_hits.reserve(nh)) || (rc = j->h_hits.reserve(nh)) ||
+        (rc = j->d_census_pairs.upload(samp.h.data(), samp.h.size())))
+        return rc;
+    hipError_t e = launch_census_d(j, M, j->d_hits.p, j->d_census_pairs.p, j->pre_stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(j->h_hits.p, j->d_hits.p, sizeof(unsigned long long) * nh, hipMemcpyDeviceToHost, j->pre_stream);
+    if ((rc = hip_fail(e, "k_sspp_census (asynchronous pre-pass)")) || (rc = j->pre_ev.record(j->pre_stream)))
+        return rc;
     struct Copies {
         std::vector<double> knots, init, limits;
         std::vector<DPair> pairs;
@@ -806,11 +783,11 @@ static int prepass_start(sspp_job* j, const double* init_ctrl, double sigma, con
              std::vector<double>(limits, limits + j->D), j->tab[kPairsFull].h, sigma, j->tables_gen};
     j->prepass_state.store(1, std::memory_order_relaxed);
     j->prepass_thread = std::thread([j, sc, c = std::move(c), t0, nh]() mutable {
-        if (hipEventSynchronize(j->pre_ev) != hipSuccess) {
+        if (j->pre_ev.wait() != SSPP_OK) {
             j->prepass_state.store(3, std::memory_order_release);
             return;
         }
-        std::vector<uint64_t> hits(j->h_hits, j->h_hits + nh);
+        std::vector<uint64_t> hits(j->h_hits.p, j->h_hits.p + nh);
         std::vector<int> wps = c2f_order(j->W);
         waypoints_from_census(hits, M, j->W, kThroughputG1, wps);
         const std::vector<int> pick(wps.begin(), wps.begin() + std::min<size_t>(wps.size(), kThroughputG1));
@@ -837,42 +814,33 @@ static void prepass_apply(sspp_job* j) {
     j->prepass_state.store(3, std::memory_order_relaxed);
     std::vector<double> uo;
     for (int i : j->pre_wps) uo.push_back((double)i / j->W);
-    double* ot = nullptr;
-    float* ot32 = nullptr;
-    int* os = nullptr;
-    if (upload_basis(uo, j->p, j->h_knots.data(), j->nknots, &ot, &os, &ot32) == SSPP_OK) {
-        j->retired.insert(j->retired.end(), {(void*)j->d_otab, (void*)j->d_otab32, (void*)j->d_ospan});
-        j->d_otab = ot; j->d_otab32 = ot32; j->d_ospan = os;
+    Dev<double> ot;
+    Dev<float> ot32;
+    Dev<int> os;
+    if (upload_basis(uo, j->p, j->h_knots.data(), j->nknots, ot, os, &ot32) == SSPP_OK) {
+        j->retired.take(std::move(j->d_otab));
+        j->retired.take(std::move(j->d_otab32));
+        j->retired.take(std::move(j->d_ospan));
+        j->d_otab = std::move(ot); j->d_otab32 = std::move(ot32); j->d_ospan = std::move(os);
         j->h_wps = j->pre_wps;
         j->wp_order = 2;
     } else {
         sspp::clear_error();
-        for (void* q : {(void*)ot, (void*)ot32, (void*)os}) if (q) (void)hipFree(q);
     }
     if (j->pre_gen == j->tables_gen && j->scene) {
-        const size_t cap = sizeof(DPair) * std::max<size_t>(1, j->scene->pairs.size());
-        bool ok = true;
-        for (PairTable& t : j->pre)
-            ok = ok && hipMalloc((void**)&t.d, cap) == hipSuccess &&
-                 (t.h.empty() || hipMemcpy(t.d, t.h.data(), sizeof(DPair) * t.h.size(), hipMemcpyHostToDevice) == hipSuccess);
-        for (int i = 0; i < 2; ++i) {
-            if (ok) {  // (the pre-pass's tables keep their flags and FP32 margin: table_set, in the thread)
-                j->retired.push_back(j->tab[i].d);
-                j->tab[i] = j->pre[i];
-            } else if (j->pre[i].d) {
-                (void)hipFree(j->pre[i].d);
+        if (table_upload(j->pre[0], j->scene) == SSPP_OK && table_upload(j->pre[1], j->scene) == SSPP_OK) {
+            // (the pre-pass's tables keep their flags and FP32 margin: table_set, in the thread)
+            for (int i = 0; i < 2; ++i) {
+                j->retired.take(std::move(j->tab[i].d));
+                j->tab[i] = std::move(j->pre[i]);
             }
-            j->pre[i].d = nullptr;
+            j->pair_order = 2;
+        } else {
+            sspp::clear_error();
+            for (PairTable& t : j->pre) t.d.reset();
         }
-        if (ok) j->pair_order = 2;
     }
     j->prepass_ms = j->pre_ms;
-}
-
-// wait for a running pre-pass and drop its result (option changes, job free)
-static void prepass_drop(sspp_job* j) {
-    if (j->prepass_thread.joinable()) j->prepass_thread.join();
-    j->prepass_state.store(3, std::memory_order_relaxed);
 }
 
 static int job_create_sspp_impl(const sspp_scene* scene, const sspp_sspp_args* a, int64_t max_batch,
@@ -924,10 +892,10 @@ static int job_create_sspp_impl(const sspp_scene* scene, const sspp_sspp_args* a
     std::vector<double> us;
     for (int i = 0; i <= W; ++i) us.push_back((double)i / W);            // collision grid
     for (int i = 0; i < W; ++i) us.push_back(W > 1 ? (double)i / (W - 1) : 0.0);  // arc-length grid
-    if ((rc = upload(&j->d_knots, a->knots, (size_t)j->nknots)) ||
-        (rc = upload_basis(us, p, a->knots, j->nknots, &j->d_tab, &j->d_span)) ||
-        (rc = upload(&j->d_init, a->init_ctrl, (size_t)n * D)) ||
-        (rc = upload(&j->d_limits, a->limits, (size_t)D))) {
+    if ((rc = j->d_knots.upload(a->knots, (size_t)j->nknots)) ||
+        (rc = upload_basis(us, p, a->knots, j->nknots, j->d_tab, j->d_span)) ||
+        (rc = j->d_init.upload(a->init_ctrl, (size_t)n * D)) ||
+        (rc = j->d_limits.upload(a->limits, (size_t)D))) {
         sspp_job_free(j);
         return rc;
     }
@@ -942,13 +910,11 @@ static int job_create_sspp_impl(const sspp_scene* scene, const sspp_sspp_args* a
     }
     // one BlockBest per workgroup and step (grown per launch when a shape needs more)
     const int64_t nrec = std::max<int64_t>(64, (max_batch + 3) / 4);
-    j->part_cap = nrec;
-    if (hipMalloc((void**)&j->d_part, sizeof(BlockBest) * nrec) != hipSuccess ||
-        hipMalloc((void**)&j->d_sync, sizeof(ArgminSync) * kMaxSteps) != hipSuccess ||
-        hipMemset(j->d_sync, 0, sizeof(ArgminSync) * kMaxSteps) != hipSuccess) {
+    if ((rc = j->d_part.reserve(nrec)) || (rc = j->d_sync.reserve(kMaxSteps)) || (rc = j->d_sync.zero())) {
         sspp_job_free(j);
-        return sspp::set_error(SSPP_E_NOMEM, "hipMalloc block partials");
+        return rc;
     }
+    j->part_cap = nrec;
     j->create_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_create).count();
     *out = j;
     return SSPP_OK;
@@ -975,28 +941,22 @@ constexpr int64_t kSplitMinCands = 16384;
 // workgroup), ready words, the survivors' rows and the argmin list, for `cands` slots of `nrd`
 // own doubles each
 static int survq_reserve(sspp_job* j, int64_t cands, int nrd) {
-    if (!j->d_sq_hdr) {
+    int rc;
+    if (!j->d_sq_hdr.p) {
         SurvQ h{};
         for (int s = 0; s < kMaxSteps; ++s) h.bestbits[s] = 0x7FF0000000000000ull;  // +inf
-        HIPCHK(hipMalloc((void**)&j->d_sq_hdr, sizeof(SurvQ)));
-        HIPCHK(hipMemcpy(j->d_sq_hdr, &h, sizeof(SurvQ), hipMemcpyHostToDevice));
+        if ((rc = j->d_sq_hdr.upload(&h, 1))) { j->d_sq_hdr.reset(); return rc; }
     }
     if (cands <= j->sq_cap && nrd == j->sq_nrd) return SSPP_OK;
     HIPCHK(hipDeviceSynchronize());  // earlier launches may still use the old buffers
-    for (void* p : {(void*)j->d_sq_rec, (void*)j->d_sq_ctrl, (void*)j->d_sq_ctrl32, (void*)j->d_sq_res,
-                    (void*)j->d_sq_orphan})
-        if (p) (void)hipFree(p);
-    j->d_sq_rec = nullptr; j->d_sq_ctrl = nullptr; j->d_sq_ctrl32 = nullptr; j->d_sq_res = nullptr;
-    j->d_sq_orphan = nullptr;
+    j->d_sq_rec.reset(); j->d_sq_ctrl.reset(); j->d_sq_ctrl32.reset(); j->d_sq_res.reset(); j->d_sq_orphan.reset();
     j->sq_cap = 0;
     const size_t n = (size_t)cands, nr = (size_t)std::max(1, nrd);
-    HIPCHK(hipMalloc((void**)&j->d_sq_rec, sizeof(unsigned long long) * n));
-    HIPCHK(hipMemset(j->d_sq_rec, 0, sizeof(unsigned long long) * n));  // ready words: not ready
-    HIPCHK(hipMalloc((void**)&j->d_sq_ctrl, sizeof(double) * n * nr));
-    HIPCHK(hipMalloc((void**)&j->d_sq_ctrl32, sizeof(float) * n * nr));
-    HIPCHK(hipMalloc((void**)&j->d_sq_res, sizeof(SurvBest) * n));
-    // handed-over tickets: one per workgroup at most, and a launch has at most `cands` workgroups
-    HIPCHK(hipMalloc((void**)&j->d_sq_orphan, sizeof(unsigned) * n));
+    // ready words: not ready.  Handed-over tickets: one per workgroup at most, and a launch has at
+    // most `cands` workgroups
+    if ((rc = j->d_sq_rec.reserve(n)) || (rc = j->d_sq_rec.zero()) || (rc = j->d_sq_ctrl.reserve(n * nr)) ||
+        (rc = j->d_sq_ctrl32.reserve(n * nr)) || (rc = j->d_sq_res.reserve(n)) || (rc = j->d_sq_orphan.reserve(n)))
+        return rc;
     j->sq_cap = cands;
     j->sq_nrd = nrd;
     return SSPP_OK;
@@ -1040,11 +1000,8 @@ static int run_sspp(sspp_job* j, const double* d_ctrl, int64_t first_id, int64_t
     const int nblk = (int)((B + cpb - 1) / cpb);
     if ((int64_t)nblk * steps > j->part_cap) {  // one BlockBest per workgroup and step
         (void)hipDeviceSynchronize();
-        if (j->d_part) (void)hipFree(j->d_part);
-        j->d_part = nullptr;
         j->part_cap = 0;
-        if (hipMalloc((void**)&j->d_part, sizeof(BlockBest) * (size_t)nblk * steps) != hipSuccess)
-            return sspp::set_error(SSPP_E_NOMEM, "hipMalloc block partials");
+        if (int rc = j->d_part.reserve((size_t)nblk * steps)) return rc;
         j->part_cap = (int64_t)nblk * steps;
     }
     SsppC2F c{};
@@ -1086,7 +1043,7 @@ static int run_sspp(sspp_job* j, const double* d_ctrl, int64_t first_id, int64_t
         const int shard_cap = ((nb_all + kSurvShards - 1) / kSurvShards) * cpb;
         int rc = survq_reserve(j, (int64_t)shard_cap * kSurvShards, nrd);
         if (rc) return rc;
-        q = SurvPtrs{j->d_sq_hdr, j->d_sq_rec, j->d_sq_ctrl, j->d_sq_ctrl32, j->d_sq_res, j->d_sq_orphan,
+        q = SurvPtrs{j->d_sq_hdr.p, j->d_sq_rec.p, j->d_sq_ctrl.p, j->d_sq_ctrl32.p, j->d_sq_res.p, j->d_sq_orphan.p,
 #ifdef SSPP_DEBUG_PROGRESS
                      j->dbg_beacon,
 #endif
@@ -1100,16 +1057,15 @@ static int run_sspp(sspp_job* j, const double* d_ctrl, int64_t first_id, int64_t
     const int nb = nblk * steps;
     j->last_queries = queries ? steps : 0;
     const size_t nd = (size_t)n * D, Q = (size_t)steps;
-    const double* qt = (const double*)j->d_qtab;  // (the set's block: a query launch's QryPtrs)
+    const double* qt = (const double*)j->d_qtab.p;  // (the set's block: a query launch's QryPtrs)
     const hipError_t e = dispatch_dp(j->D, j->p, [&](auto dof, auto deg) {
         constexpr int DV = decltype(dof)::value, PV = decltype(deg)::value;
         if (!queries) return entry_c2f_p<DV, PV>(c, j, o, nb, st, t);
         return entry_c2f_p<DV, PV>(c, j, o, nb, st, t,
-                                   QryPtrs{qt, qt + Q * nd, qt + Q * (nd + D), j->d_qtab + Q * (nd + D + 1)});
+                                   QryPtrs{qt, qt + Q * nd, qt + Q * (nd + D), j->d_qtab.p + Q * (nd + D + 1)});
     });
     j->last_split = split_used;
-    if (e != hipSuccess) return hip_fail(e, queries ? "k_sspp_c2f query launch" : "k_sspp_c2f launch");
-    return SSPP_OK;
+    return hip_fail(e, queries ? "k_sspp_c2f query launch" : "k_sspp_c2f launch");
 }
 
 extern "C" int sspp_job_sample_score(sspp_job* j, int64_t first_id, int64_t B, double* d_arc,
@@ -1137,37 +1093,25 @@ extern "C" int sspp_job_update_sspp(sspp_job* j, const double* init_ctrl, double
         std::memcmp(j->h_stage.data(), init_ctrl, sizeof(double) * nd) == 0 &&
         std::memcmp(j->h_stage.data() + nd, limits, sizeof(double) * j->D) == 0)
         return SSPP_OK;
-    const bool pairs = j->tab[kPairsFull].d && j->scene;
+    const bool pairs = j->tab[kPairsFull].d.p && j->scene;
     const size_t vbytes = sizeof(double) * (nd + j->D);
     const size_t need = vbytes + (pairs ? 2 * sizeof(DPair) * j->scene->pairs.size() : 0);
     // the pinned staging is the source of the previous update's copies until they complete
-    if (j->upd_pending) {
-        HIPCHK(hipEventSynchronize(j->upd_ev));
-        j->upd_pending = false;
-    }
-    if (need > j->h_pin_bytes) {
-        if (j->h_pin) HIPCHK(hipHostFree(j->h_pin));
-        j->h_pin = nullptr;
-        j->h_pin_bytes = 0;
-        HIPCHK(hipHostMalloc((void**)&j->h_pin, need, hipHostMallocDefault));
-        j->h_pin_bytes = need;
-    }
-    if (!j->upd_ev) HIPCHK(hipEventCreateWithFlags(&j->upd_ev, hipEventDisableTiming));
+    int rc;
+    if ((rc = j->upd.wait()) || (rc = j->upd.reserve(need))) return rc;
     j->h_stage.assign(init_ctrl, init_ctrl + nd);
     j->h_stage.insert(j->h_stage.end(), limits, limits + j->D);
     j->sigma = sigma;
-    std::memcpy(j->h_pin, j->h_stage.data(), vbytes);
-    const double* pv = (const double*)j->h_pin;
-    HIPCHK(hipMemcpyAsync(j->d_init, pv, sizeof(double) * nd, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(j->d_limits, pv + nd, sizeof(double) * j->D, hipMemcpyHostToDevice, st));
+    std::memcpy(j->upd.buf.p, j->h_stage.data(), vbytes);
+    const double* pv = (const double*)j->upd.buf.p;
+    HIPCHK(hipMemcpyAsync(j->d_init.p, pv, sizeof(double) * nd, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(j->d_limits.p, pv + nd, sizeof(double) * j->D, hipMemcpyHostToDevice, st));
     if (pairs) {
         ++j->tables_gen;  // a pre-pass still running ordered the previous values' tables
-        const int rc = set_job_tables(j, init_ctrl, sigma, limits, j->pair_order == 0 ? 0 : 1, false, stream, vbytes);
+        rc = set_job_tables(j, init_ctrl, sigma, limits, j->pair_order == 0 ? 0 : 1, false, stream, vbytes);
         if (rc) return rc;
     }
-    HIPCHK(hipEventRecord(j->upd_ev, st));
-    j->upd_pending = true;
-    return SSPP_OK;
+    return j->upd.record(st);
 }
 
 // A query set for query launches: Q independent queries (initial spline, sigma, limits, seed each)
@@ -1184,27 +1128,23 @@ extern "C" int sspp_job_set_queries(sspp_job* j, int Q, const double* init_ctrl,
     const size_t nd = (size_t)j->n * j->D, D = (size_t)j->D;
     const sspp_scene* sc = j->scene;
     const bool pairs = sc && !sc->pairs.empty();
-    const size_t vcap = sizeof(double) * kMaxSteps * (nd + D + 2);
+    const size_t vwords = (size_t)kMaxSteps * (nd + D + 2), vcap = sizeof(double) * vwords;
     const size_t pcap = pairs ? sizeof(DPair) * sc->pairs.size() : 0;
     hipStream_t st = (hipStream_t)stream;
-    if (j->q_pending) {  // the staging is the source of the previous set's copies until they complete
-        HIPCHK(hipEventSynchronize(j->q_ev));
-        j->q_pending = false;
-    }
-    if (!j->d_qtab) {  // once per job, sized for kMaxSteps queries
-        HIPCHK(hipMalloc((void**)&j->d_qtab, vcap));
-        if (pairs) HIPCHK(hipMalloc((void**)&j->tab[kPairsQueries].d, pcap));
-        HIPCHK(hipHostMalloc((void**)&j->h_qpin, vcap + pcap, hipHostMallocDefault));
-        HIPCHK(hipEventCreateWithFlags(&j->q_ev, hipEventDisableTiming));
-    }
-    double* hv = (double*)j->h_qpin;
+    PairTable& tq = j->tab[kPairsQueries];
+    int rc;
+    // the staging is the source of the previous set's copies until they complete; the buffers are
+    // allocated once per job, sized for kMaxSteps queries and every pair of the scene
+    if ((rc = j->qst.wait()) || (rc = j->d_qtab.reserve(vwords)) || (pairs && (rc = tq.d.reserve(sc->pairs.size()))) ||
+        (rc = j->qst.reserve(vcap + pcap)))
+        return rc;
+    double* hv = (double*)j->qst.buf.p;
     const size_t nv = (size_t)Q * (nd + D + 2);
     std::memcpy(hv, init_ctrl, sizeof(double) * Q * nd);
     std::memcpy(hv + Q * nd, limits, sizeof(double) * Q * D);
     std::memcpy(hv + Q * (nd + D), sigma, sizeof(double) * Q);
     std::memcpy(hv + Q * (nd + D + 1), seed, sizeof(uint64_t) * Q);
-    HIPCHK(hipMemcpyAsync(j->d_qtab, hv, sizeof(double) * nv, hipMemcpyHostToDevice, st));
-    PairTable& tq = j->tab[kPairsQueries];
+    HIPCHK(hipMemcpyAsync(j->d_qtab.p, hv, sizeof(double) * nv, hipMemcpyHostToDevice, st));
     std::vector<DPair> reach;
     if (pairs) {
         std::vector<ReachBox> lo((size_t)Q), hi((size_t)Q);
@@ -1215,12 +1155,11 @@ extern "C" int sspp_job_set_queries(sspp_job* j, int Q, const double* init_ctrl,
     }
     table_set(tq, sc, std::move(reach));
     if (!tq.h.empty()) {
-        unsigned char* pp = j->h_qpin + vcap;
+        unsigned char* pp = j->qst.buf.p + vcap;
         std::memcpy(pp, tq.h.data(), sizeof(DPair) * tq.h.size());
-        HIPCHK(hipMemcpyAsync(tq.d, pp, sizeof(DPair) * tq.h.size(), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(tq.d.p, pp, sizeof(DPair) * tq.h.size(), hipMemcpyHostToDevice, st));
     }
-    HIPCHK(hipEventRecord(j->q_ev, st));
-    j->q_pending = true;
+    if ((rc = j->qst.record(st))) return rc;
     j->nq = Q;
     j->view_q = 1;
     return SSPP_OK;
@@ -1258,7 +1197,7 @@ extern "C" int sspp_job_set_option(sspp_job* j, int key, int64_t value) {
             return SSPP_OK;
         case SSPP_OPT_ORDER: {
             if (j->kind != 0 || value < 0 || value > 2) return sspp::set_error(SSPP_E_INVAL, "SSPP_OPT_ORDER: 0, 1 or 2");
-            prepass_drop(j);
+            j->prepass_drop();
             HIPCHK(hipDeviceSynchronize());  // earlier launches may still read the tables
             const size_t nd = (size_t)j->n * j->D;
             return set_job_tables(j, j->h_stage.data(), j->sigma, j->h_stage.data() + nd, (int)value, true, nullptr);
@@ -1331,10 +1270,10 @@ extern "C" int sspp_job_get_option(const sspp_job* j, int key, int64_t* value) {
         case SSPP_OPT_SPLIT_HANDOFFS:
         case SSPP_OPT_SPLIT_LOST: {  // synchronous read of the queue header (tests, diagnostics)
             *value = 0;
-            if (!j->d_sq_hdr) return SSPP_OK;
+            if (!j->d_sq_hdr.p) return SSPP_OK;
             SurvQ h;
             HIPCHK(hipDeviceSynchronize());
-            HIPCHK(hipMemcpy(&h, j->d_sq_hdr, sizeof(SurvQ), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(&h, j->d_sq_hdr.p, sizeof(SurvQ), hipMemcpyDeviceToHost));
             *value = (int64_t)(key == SSPP_OPT_SPLIT_HANDOFFS ? h.handoffs : h.lost_total);
             return SSPP_OK;
         }
@@ -1378,23 +1317,21 @@ extern "C" int sspp_job_create_tsp(const sspp_scene* scene, const sspp_tsp_args*
     std::vector<double> us;
     const double du = 1.0 / cp;
     for (int i = 0; i <= cp; ++i) us.push_back((double)i * du);  // eval_one_pass: s(i * du)
-    if ((rc = upload(&j->d_knots, knots.data(), knots.size())) ||
-        (rc = upload_basis(us, 2, knots.data(), (int)knots.size(), &j->d_tab, &j->d_span)) ||
-        (rc = upload(&j->d_Minv, Minv.data(), Minv.size())) ||
-        (rc = upload(&j->d_mean, K ? a->mean : zero.data(), K ? (size_t)K * 4 : 4)) ||
-        (rc = upload(&j->d_sigma, K ? a->sigma : zero.data(), K ? (size_t)K * 4 : 4))) {
+    if ((rc = j->d_knots.upload(knots.data(), knots.size())) ||
+        (rc = upload_basis(us, 2, knots.data(), (int)knots.size(), j->d_tab, j->d_span)) ||
+        (rc = j->d_Minv.upload(Minv.data(), Minv.size())) ||
+        (rc = j->d_mean.upload(K ? a->mean : zero.data(), K ? (size_t)K * 4 : 4)) ||
+        (rc = j->d_sigma.upload(K ? a->sigma : zero.data(), K ? (size_t)K * 4 : 4))) {
         sspp_job_free(j);
         return rc;
     }
     // one record per workgroup: k_tsp's blocks, or one per candidate for k_tsp_pp
     const int64_t nrec = std::max<int64_t>(nblk, std::min<int64_t>(max_batch, kTspPpMaxBatch));
-    j->part_cap = nrec;
-    if (hipMalloc((void**)&j->d_part, sizeof(BlockBest) * nrec) != hipSuccess ||
-        hipMalloc((void**)&j->d_sync, sizeof(ArgminSync)) != hipSuccess ||
-        hipMemset(j->d_sync, 0, sizeof(ArgminSync)) != hipSuccess) {
+    if ((rc = j->d_part.reserve(nrec)) || (rc = j->d_sync.reserve(1)) || (rc = j->d_sync.zero())) {
         sspp_job_free(j);
-        return sspp::set_error(SSPP_E_NOMEM, "hipMalloc block partials");
+        return rc;
     }
+    j->part_cap = nrec;
     *out = j;
     return SSPP_OK;
 }
@@ -1454,8 +1391,8 @@ static int run_tsp(sspp_job* j, const double* d_vias, int64_t first_id, int64_t 
     if (!d_L || !d_Cnf || !d_Cwf || !d_status || !d_cost)
         return sspp::set_error(SSPP_E_INVAL, "null output");
     TspK k = tsp_k(j, first_id, B);
-    const double* mean = j->d_mean;
-    const double* sigma = j->d_sigma;
+    const double* mean = j->d_mean.p;
+    const double* sigma = j->d_sigma.p;
     if (ces) {
         if (d_vias) return sspp::set_error(SSPP_E_INVAL, "CES slot mode samples its own via sets");
         k.ces = 1; k.fixed = ces->fixed; k.nfixed = ces->nfixed;
@@ -1474,18 +1411,18 @@ static int run_tsp(sspp_job* j, const double* d_vias, int64_t first_id, int64_t 
     const int npg = (k.sc.npairs + 7) / 8;
     int mode = pp ? 1 : 0;
     if (pp && npg > 1 && pp_opt != 1 && B <= kTspPpMaxBatch) {
-        if (!j->d_pp_arrive) {
-            const int64_t cap = std::min<int64_t>(j->max_batch, kTspPpMaxBatch);
-            if (hipMalloc((void**)&j->d_pp_nd, sizeof(unsigned) * 4096 * (size_t)cap) != hipSuccess ||
-                hipMalloc((void**)&j->d_pp_term, sizeof(double) * 4096 * (size_t)cap) != hipSuccess ||
-                hipMalloc((void**)&j->d_pp_arrive, sizeof(unsigned) * (size_t)cap) != hipSuccess ||
-                hipMemset(j->d_pp_arrive, 0, sizeof(unsigned) * (size_t)cap) != hipSuccess)
-                return sspp::set_error(SSPP_E_NOMEM, "hipMalloc k_tsp_pp2 records");
-            j->pp_cap = cap;
+        if (!j->d_pp_arrive.p) {  // (the last of the three; its counters start at zero)
+            const size_t cap = (size_t)std::min<int64_t>(j->max_batch, kTspPpMaxBatch);
+            int rc;
+            if ((rc = j->d_pp_nd.reserve(4096 * cap)) || (rc = j->d_pp_term.reserve(4096 * cap)) ||
+                (rc = j->d_pp_arrive.reserve(cap)))
+                return rc;
+            if ((rc = j->d_pp_arrive.zero())) { j->d_pp_arrive.reset(); return rc; }
+            j->pp_cap = (int64_t)cap;
         }
         if (B <= j->pp_cap) {
             mode = 2;
-            k.rec_nd = j->d_pp_nd; k.rec_term = j->d_pp_term; k.arrive = j->d_pp_arrive; k.npg = npg;
+            k.rec_nd = j->d_pp_nd.p; k.rec_term = j->d_pp_term.p; k.arrive = j->d_pp_arrive.p; k.npg = npg;
         }
     }
     // the deferred-polygon form of k_tsp (mode 3): one waypoint per lane, few pairs, some of them
@@ -1505,9 +1442,7 @@ static int run_tsp(sspp_job* j, const double* d_vias, int64_t first_id, int64_t 
     hipError_t e0 = entry_tsp<0>(k, j, nblk, mean, sigma, d_vias, d_vias_out, d_L, d_Cnf, d_Cwf, d_cost, d_status,
                                  d_best, st, mode);
     if (e0 != hipSuccess) return hip_fail(e0, "k_tsp launch");
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_tsp launch");
-    return SSPP_OK;
+    return hip_fail(hipGetLastError(), "k_tsp launch");
 }
 
 void sspp::job_set_ctrl_feasible_only(sspp_job* j, int on) {
@@ -1543,7 +1478,7 @@ int sspp::tsp_eval_ces_group(sspp_job* const* jobs, const TspCesEval* evs, const
                     j->w_col == j0->w_col && j->floor_z_min == j0->floor_z_min &&
                     j->floor_margin == j0->floor_margin && j->floor_scale == j0->floor_scale &&
                     j->tsp_generic == j0->tsp_generic && j->tsp_form == j0->tsp_form &&
-                    j->d_tab && j->h_knots == j0->h_knots && evs[g].samples == evs[0].samples &&
+                    j->d_tab.p && j->h_knots == j0->h_knots && evs[g].samples == evs[0].samples &&
                     evs[g].slot0 == 0;
         for (int i = 0; i < 4; ++i) same = same && j->lo[i] == j0->lo[i] && j->hi[i] == j0->hi[i];
         if (!same) return sspp::set_error(SSPP_E_UNSUPPORTED, "goals differ beyond start / end / seed");
@@ -1575,8 +1510,7 @@ int sspp::tsp_eval_ces_group(sspp_job* const* jobs, const TspCesEval* evs, const
         jobs[g]->last_rep = k.rep;
     }
     hipError_t e = entry_tsp_group<0>(k, goals, j0, goals.nblk * G, (hipStream_t)stream, mode);
-    if (e != hipSuccess) return hip_fail(e, "k_tsp_group launch");
-    return SSPP_OK;
+    return hip_fail(e, "k_tsp_group launch");
 }
 
 extern "C" int sspp_job_tsp_sample_score(sspp_job* j, int64_t first_id, int64_t B, double* d_L, double* d_Cnf,
@@ -1611,42 +1545,7 @@ extern "C" int sspp_job_info(const sspp_job* j, int* lpc, int* cpb_out, int* thr
     return SSPP_OK;
 }
 
-extern "C" void sspp_job_free(sspp_job* j) {
-    if (!j) return;
-    prepass_drop(j);
-    if (j->pre_stream) (void)hipStreamSynchronize(j->pre_stream);
-    for (void* q : {(void*)j->d_sq_hdr, (void*)j->d_sq_rec, (void*)j->d_sq_ctrl, (void*)j->d_sq_ctrl32,
-                    (void*)j->d_sq_res, (void*)j->d_sq_orphan})
-        if (q) (void)hipFree(q);
-    for (void* q : j->retired) if (q) (void)hipFree(q);
-    for (void* q : {(void*)j->d_hits, (void*)j->d_census_pairs}) if (q) (void)hipFree(q);
-    if (j->h_hits) (void)hipHostFree(j->h_hits);
-    if (j->pre_ev) (void)hipEventDestroy(j->pre_ev);
-
-    for (double* p : {j->d_knots, j->d_tab, j->d_init, j->d_limits, j->d_Minv, j->d_mean, j->d_sigma})
-        if (p) (void)hipFree(p);
-    if (j->d_span) (void)hipFree(j->d_span);
-    if (j->d_otab) (void)hipFree(j->d_otab);
-    if (j->d_otab32) (void)hipFree(j->d_otab32);
-    for (const PairTable& t : j->tab) if (t.d) (void)hipFree(t.d);
-    if (j->d_ospan) (void)hipFree(j->d_ospan);
-    if (j->d_part) (void)hipFree(j->d_part);
-    if (j->d_sync) (void)hipFree(j->d_sync);
-    for (void* q : {(void*)j->d_pp_nd, (void*)j->d_pp_term, (void*)j->d_pp_arrive})
-        if (q) (void)hipFree(q);
-    if (j->upd_ev) {
-        (void)hipEventSynchronize(j->upd_ev);
-        (void)hipEventDestroy(j->upd_ev);
-    }
-    if (j->h_pin) (void)hipHostFree(j->h_pin);
-    if (j->q_ev) {
-        (void)hipEventSynchronize(j->q_ev);
-        (void)hipEventDestroy(j->q_ev);
-    }
-    if (j->d_qtab) (void)hipFree(j->d_qtab);
-    if (j->h_qpin) (void)hipHostFree(j->h_qpin);
-    delete j;
-}
+extern "C" void sspp_job_free(sspp_job* j) { delete j; }
 
 extern "C" int sspp_best_reduce_device(const sspp_best* d_parts, int n, sspp_best* d_out,
                                        void* stream) {
@@ -1655,9 +1554,7 @@ extern "C" int sspp_best_reduce_device(const sspp_best* d_parts, int n, sspp_bes
     static_assert(sizeof(BlockBest) == sizeof(sspp_best), "layout");
     hipLaunchKernelGGL(k_argmin, dim3(1), dim3(kArgminThreads), 0, (hipStream_t)stream,
                        reinterpret_cast<const BlockBest*>(d_parts), n, d_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_argmin launch");
-    return SSPP_OK;
+    return hip_fail(hipGetLastError(), "k_argmin launch");
 }
 
 // ---------------------------------------------------------------- step enqueue (host executor)
@@ -1782,9 +1679,13 @@ extern "C" int sspp_best_reduce_steps(const sspp_best* d_parts, int R, int G, ss
     if (!d_parts || !d_out || R < 1 || G < 1) return sspp::set_error(SSPP_E_INVAL, "sspp_best_reduce_steps: bad argument");
     hipLaunchKernelGGL(k_argmin_steps, dim3(G), dim3(64), 0, (hipStream_t)stream,
                        reinterpret_cast<const BlockBest*>(d_parts), R, G, d_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k_argmin_steps launch");
-    return SSPP_OK;
+    return hip_fail(hipGetLastError(), "k_argmin_steps launch");
+}
+
+// device buffers, pinned buffers and events the owning types (sspp_own.h) hold alive in this process
+extern "C" int sspp_debug_live_resources(long long out[3]) {
+    for (int i = 0; i < 3; ++i) out[i] = g_live[i].load(std::memory_order_relaxed);
+    return 0;
 }
 
 #ifdef SSPP_TSP_STATS
@@ -1837,8 +1738,7 @@ extern "C" int sspp_device_count(int* n) {
     int c = 0;
     hipError_t e = hipGetDeviceCount(&c);
     if (n) *n = (e == hipSuccess) ? c : 0;
-    if (e != hipSuccess) return hip_fail(e, "hipGetDeviceCount");
-    return SSPP_OK;
+    return hip_fail(e, "hipGetDeviceCount");
 }
 
 

@@ -7,6 +7,10 @@
 
 #include "sspp_kern.h"
 
+// the owning types report HIP failures through these (sspp_capi.cpp in the library)
+int sspp::set_error(int code, const std::string&) { return code; }
+void sspp::clear_error() {}
+
 static sspd::DGeom geom(int type, double rbound) {
     sspd::DGeom g{};
     g.mat[0] = g.mat[4] = g.mat[8] = 1.0;
@@ -19,6 +23,14 @@ static sspd::DPair pair(int gm, int otype, double orbound, double margin) {
     p.omat[0] = p.omat[4] = p.omat[8] = 1.0;
     p.orbound = orbound; p.margin = margin;
     return p;
+}
+// a host address (or none) as a stand-in for a buffer's device copy, counted as the buffer counts
+// its own allocations, so that the release() below leaves the live count where it was
+template <class T>
+static void adopt(sspo::Dev<T>& d, T* p) {
+    (void)d.release();
+    d.p = p;
+    if (p) sspo::live_add(sspo::kLiveDev, 1);
 }
 static void row(const sspp_scene* sc, std::vector<sspd::DPair> pairs) {
     PairTable t;
@@ -50,15 +62,18 @@ int main() {
 
     // the scene's own pairs are {box_cyl, cyl_cyl}; a table with a device copy overrides them
     s.pairs = {box_cyl, cyl_cyl};
-    s.d_pairs = &s.pairs[0];  // (never read: only the pointers are compared)
+    adopt(s.d_pairs, &s.pairs[0]);  // (never read: only the pointers are compared; released below)
     j.scene = &s;
     PairTable& t = j.tab[kPairsSampled];
     table_set(t, &s, {box_box});
     for (int with_copy = 0; with_copy < 2; ++with_copy) {
-        t.d = with_copy ? &t.h[0] : nullptr;
+        adopt(t.d, with_copy ? &t.h[0] : nullptr);
         const sspk::KScene k = sspk::kscene_job(&j, t);
         const sspk::SceneT T = sspk::scene_t_job(&j, t);
-        std::printf("%d %d %d %d\n", k.npairs, k.cylbox, k.onegeom, T.pairs == t.d ? 1 : T.pairs == s.d_pairs ? 0 : -1);
+        std::printf("%d %d %d %d\n", k.npairs, k.cylbox, k.onegeom, T.pairs == t.d.p ? 1 : T.pairs == s.d_pairs.p ? 0 : -1);
     }
-    return 0;
+    // the host addresses stood in for device copies: their owners must not free them
+    (void)t.d.release();
+    (void)s.d_pairs.release();
+    return sspo::g_live[sspo::kLiveDev].load() == 0 ? 0 : 1;
 }
