@@ -1582,8 +1582,13 @@ constexpr double kHullPad = 1e-9;
 // plane above rbound + margin (+ kHullPad for rounding) rules out a contact — the plane-box
 // corners satisfy t >= h - sum_j |n.a_j| e_j >= h - |e| = h - rbound (Cauchy-Schwarz).
 // A box partner that passes the sphere test is tested once more against the moving geom's
-// bounding sphere (centre in the box frame, distance to the box): a geom whose sphere stays
-// farther than rbound + margin (+ kHullPad) from the box cannot touch it.  This rejects, for a
+// bounding sphere (centre in the box frame): a geom whose centre lies farther than rbound +
+// margin (+ kHullPad) beyond one of the box's faces, along that face's normal, cannot touch it.
+// Per face axis and not the Euclidean distance to the box: box-box contact is the SAT's "no
+// axis separates by the margin", which off an edge or a corner of the partner holds for boxes
+// whose true distance exceeds the margin; the partner's face axis j does separate them when
+// |l_j| - size_j > rbound + margin, since the moving box's extent along any axis is at most
+// its rbound.  (The distance-based narrowphases are covered a fortiori.)  This rejects, for a
 // few dozen flops, the near-but-apart pairs (a block above a large table) before the 15-axis SAT.
 SSPP_HD bool pair_near(const DPair& pr, double rg, const double* gp,
                                           const double* op, const double* om) {
@@ -1596,10 +1601,9 @@ SSPP_HD bool pair_near(const DPair& pr, double rg, const double* gp,
             const double lx = fma(om[6], dc[2], fma(om[3], dc[1], om[0] * dc[0]));
             const double ly = fma(om[7], dc[2], fma(om[4], dc[1], om[1] * dc[0]));
             const double lz = fma(om[8], dc[2], fma(om[5], dc[1], om[2] * dc[0]));
-            const double ex = fmax(fabs(lx) - pr.osize[0], 0.0), ey = fmax(fabs(ly) - pr.osize[1], 0.0),
-                         ez = fmax(fabs(lz) - pr.osize[2], 0.0);
+            const double out = fmax(fmax(fabs(lx) - pr.osize[0], fabs(ly) - pr.osize[1]), fabs(lz) - pr.osize[2]);
             const double lim = rg + pr.margin + in_sgpr(kHullPad);  // (the pad: see deep_thr)
-            return !(fma(ez, ez, fma(ey, ey, ex * ex)) > lim * lim);
+            return !(out > lim);
         }
         return true;
     }

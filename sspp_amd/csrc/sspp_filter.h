@@ -113,12 +113,10 @@ SSPP_HD int pair_near32(float ro, int otype, float margin, const float* osize, f
             const float lx = fmaf(om[6], dc[2], fmaf(om[3], dc[1], om[0] * dc[0]));
             const float ly = fmaf(om[7], dc[2], fmaf(om[4], dc[1], om[1] * dc[0]));
             const float lz = fmaf(om[8], dc[2], fmaf(om[5], dc[1], om[2] * dc[0]));
-            const float ex = fmaxf(fabsf(lx) - osize[0], 0.0f), ey = fmaxf(fabsf(ly) - osize[1], 0.0f),
-                        ez = fmaxf(fabsf(lz) - osize[2], 0.0f);
+            const float out = fmaxf(fmaxf(fabsf(lx) - osize[0], fabsf(ly) - osize[1]), fabsf(lz) - osize[2]);
             const float lim = rg + margin + pad;
-            const float e2 = fmaf(ez, ez, fmaf(ey, ey, ex * ex));
-            if (e2 > (lim + eps) * (lim + eps)) return kNo;
-            if (!(e2 < (lim - eps) * (lim - eps))) r = kAmb;
+            if (out > lim + eps) return kNo;
+            if (!(out < lim - eps)) r = kAmb;
         }
         return r;
     }

@@ -53,6 +53,8 @@ ENDS = (-0.0, 0.0)
 
 
 def offsets_of(c):
+    if "offsets" in c:   # a scene's own offsets (tests/envelope_scenes.py: relative to its table's eps)
+        return c["offsets"]
     return OFFSETS if "capsule" in c["pair"] or "yaw" in c else OFFSETS + ENDS
 MARGINS = (0.0, 1e-3, 1e-2)
 THETAS = (5e-7, 1e-6, 2e-6, 1e-5, 3e-5)
@@ -468,8 +470,15 @@ def tsp_cases(name):
 
 # ------------------------------------------------------------------ bisection
 def _line(ref, c):
+    """The line the case's root moves on.  Hooks of a case (tests/envelope_scenes.py; none of this
+    module's cases sets one): "origin", a world point that stands in for the target's position (a
+    plane touched far from its origin, a target that hangs on a mover); "offset", a function of the
+    quaternion giving the world vector from the root to the geom that is to touch (the line is the
+    geom's, the root's lies that vector back)."""
     g = ref.geom(c["target"])
-    pos = np.asarray(ref.ref["geom_pos"][g], float)
+    pos = np.asarray(c["origin"] if "origin" in c else ref.ref["geom_pos"][g], float)
+    if "offset" in c:
+        pos = pos - c["offset"](c["quat"])
     if c["frame"] == "target":
         M = ref_mat(ref, c["target"])
         return pos + M @ c["anchor"], M @ c["d"]
@@ -478,6 +487,8 @@ def _line(ref, c):
 
 def _pose(ref, c, a, d, t):
     p = a + t * d
+    if "pose" in c:   # a case's own qpos row from the moved root and the quaternion (two movers)
+        return c["pose"](p, c["quat"])
     if ref.mode == 1:
         return np.array([p[0], p[1], p[2], c["yaw"]])
     return np.concatenate([p, c["quat"]])
@@ -489,7 +500,7 @@ def bisect_touch(ref, c, deep=False):
     a, d = _line(ref, c)
     hit = (lambda t: ref.contacts(_pose(ref, c, a, d, t))[1] > 0) if deep else \
         (lambda t: ref.contacts(_pose(ref, c, a, d, t))[0] > 0)
-    lo, hi = 0.0, T_CLEAR
+    lo, hi = 0.0, c.get("t_clear", T_CLEAR)
     if not hit(lo) or hit(hi):
         raise AssertionError("case %s / %s on %s does not go from overlap to clear" % (c["pair"], c["feature"], c["target"]))
     for _ in range(N_BISECT):
@@ -505,19 +516,26 @@ def bisect_touch(ref, c, deep=False):
 
 def poses_of(ref, cases, deep=False):
     """Every case's poses: dict(q [n, D], off [n], case [n] (index into cases), d [n, 3],
-    touch [len(cases)])."""
-    q, off, idx, dirs, touch = [], [], [], [], []
+    touch [len(cases)]); with a case that writes its own qpos row ("pose"), also back [n, D], each
+    pose moved 1 m on along d (where the moved coordinates are is the case's to say)."""
+    q, off, idx, dirs, touch, back = [], [], [], [], [], []
+    own_rows = any("pose" in c for c in cases)
     for k, c in enumerate(cases):
         a, d = _line(ref, c)
         c["d_world"] = d
         t_lo, t = bisect_touch(ref, c, deep)
         touch.append(t)
         for o in offsets_of(c):
-            q.append(_pose(ref, c, a, d, (t_lo if np.signbit(o) else t) if o == 0.0 else t + o))
+            at = (t_lo if np.signbit(o) else t) if o == 0.0 else t + o
+            q.append(_pose(ref, c, a, d, at))
             off.append(o)
             idx.append(k)
             dirs.append(d)
+            if own_rows:
+                back.append(_pose(ref, c, a, d, at + 1.0))
     out = dict(q=np.array(q), off=np.array(off), case=np.array(idx), d=np.array(dirs), touch=np.array(touch))
+    if own_rows:
+        out["back"] = np.array(back)
     for v in out.values():
         v.setflags(write=False)
     return out

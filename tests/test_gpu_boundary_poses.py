@@ -74,12 +74,16 @@ def world(cuda, tmp_path_factory):
 # ------------------------------------------------------------------ SamplingPathPlanner
 def candidates(P, variant):
     """[n, N_CTRL, 7] control rows per pose.  "equal": every row the pose.  "approach": row 0 the
-    pose, every other row the pose moved 1 m back along d; "mirrored": the pose in the last row."""
+    pose, every other row the pose moved 1 m back along d (P["back"] where the set's cases write
+    their own qpos rows); "mirrored": the pose in the last row."""
     q = P["q"]
     ctrl = np.repeat(q[:, None, :], N_CTRL, axis=1).copy()
     if variant != "equal":
-        back = q.copy()
-        back[:, :3] += P["d"]
+        if "back" in P:
+            back = P["back"]
+        else:
+            back = q.copy()
+            back[:, :3] += P["d"]
         ctrl[:] = back[:, None, :]
         ctrl[:, 0 if variant == "approach" else -1] = q
     return ctrl
@@ -126,11 +130,11 @@ def sspp_reference(world, b, kind, margin, knots, variant):
     return src.memo[key]
 
 
-def run_score_ctrl(b, knots, ctrl0, ctrl, nt, g1, f32, order):
+def run_score_ctrl(b, knots, ctrl0, ctrl, nt, g1, f32, order, limits=LIMITS):
     import sspp_amd as S
     import torch
     n = len(ctrl)
-    job = S.SsppJob(b.scene, knots, 3, ctrl0, 0.0, LIMITS, W, seed=SEED, max_batch=n)
+    job = S.SsppJob(b.scene, knots, 3, ctrl0, 0.0, limits, W, seed=SEED, max_batch=n)
     job.set_shape(nt, g1)
     job.set_option(S.OPT_F32, f32)
     job.set_option(S.OPT_ORDER, order)
@@ -182,44 +186,52 @@ SAMPLE_B = 4
 SAMPLE_SIGMA = 1e-6
 
 
-@pytest.mark.parametrize("margin", BP.MARGINS)
-@pytest.mark.parametrize("kind", BP.SSPP_KINDS)
-def test_sspp_sampled_around_boundary_poses(world, kind, margin):
-    """sample_score with sigma = 1e-6 and start = end = a boundary pose: the kernel's own sampler
-    and its FP32 copies feed the scan.  One job per pose (the initial spline is the job's), a few
-    candidates each; sampled control points bit-equal to the oracle's, feasibility for whatever
-    the reference says of them; both outcomes occur."""
+def sampled_around(b, P, score, dof=D, limits=LIMITS):
+    """sample_score with sigma = 1e-6 and start = end = each pose of P: one job per pose (the
+    initial spline is the job's), a few candidates each; sampled control points bit-equal to the
+    oracle's, feasibility for whatever the reference (score(knots, ctrl) -> (arc, feasible)) says
+    of them; both outcomes occur.  Returns the jobs."""
     import sspp_amd as S
     import torch
-    b = world["sspp"](kind, margin, "hull")
-    _, cases, P = BP.sspp_set(world["root"], kind, margin)
     n = len(P["q"])
     arc = torch.empty(n * SAMPLE_B, dtype=torch.float64, device="cuda")
     feas = torch.empty(n * SAMPLE_B, dtype=torch.uint8, device="cuda")
-    ctrl = torch.empty((n * SAMPLE_B, N_CTRL, D), dtype=torch.float64, device="cuda")
+    ctrl = torch.empty((n * SAMPLE_B, N_CTRL, dof), dtype=torch.float64, device="cuda")
     best = torch.zeros((n, 4), dtype=torch.int64, device="cuda")
-    jobs, ctrl_o = [], np.empty((n * SAMPLE_B, N_CTRL, D))
+    jobs, ctrl_o = [], np.empty((n * SAMPLE_B, N_CTRL, dof))
     knots = None
     for i, q in enumerate(P["q"]):
         knots, ctrl0 = linear_init(q, q, N_CTRL)
-        job = S.SsppJob(b.scene, knots, 3, ctrl0, SAMPLE_SIGMA, LIMITS, W, seed=SEED, max_batch=SAMPLE_B)
+        job = S.SsppJob(b.scene, knots, 3, ctrl0, SAMPLE_SIGMA, limits, W, seed=SEED, max_batch=SAMPLE_B)
         s = slice(i * SAMPLE_B, (i + 1) * SAMPLE_B)
         job.sample_score(i * SAMPLE_B, SAMPLE_B, arc[s], feas[s], best[i], ctrl_out=ctrl[s])
         jobs.append(job)
-        ctrl_o[s] = O.sample_sspp(ctrl0, 3, SAMPLE_SIGMA, LIMITS, SEED, i * SAMPLE_B, SAMPLE_B)
+        ctrl_o[s] = O.sample_sspp(ctrl0, 3, SAMPLE_SIGMA, limits, SEED, i * SAMPLE_B, SAMPLE_B)
     torch.cuda.synchronize()
     assert np.array_equal(_np(ctrl), ctrl_o)
-    arc_o, feas_o = reference_score(world["sspp"](kind, margin, "small") if b.r.has_capsule else b, knots, ctrl_o)
+    arc_o, feas_o = score(knots, ctrl_o)
     assert 0 < int(feas_o.sum()) < len(feas_o)
     np.testing.assert_array_equal(_np(feas), feas_o)
     assert arc_err(_np(arc), arc_o) <= COST_TOL
     for i in range(0, n, 7):
         s = slice(i * SAMPLE_B, (i + 1) * SAMPLE_B)
         assert_parity(_np(arc[s]), _np(feas[s]), S.decode_best(best[i]), arc_o[s], feas_o[s], first=i * SAMPLE_B)
+    return jobs
+
+
+@pytest.mark.parametrize("margin", BP.MARGINS)
+@pytest.mark.parametrize("kind", BP.SSPP_KINDS)
+def test_sspp_sampled_around_boundary_poses(world, kind, margin):
+    """sample_score around every boundary pose (sampled_around): the kernel's own sampler and its
+    FP32 copies feed the scan."""
+    b = world["sspp"](kind, margin, "hull")
+    _, cases, P = BP.sspp_set(world["root"], kind, margin)
+    src = world["sspp"](kind, margin, "small") if b.r.has_capsule else b
+    jobs = sampled_around(b, P, lambda knots, ctrl: reference_score(src, knots, ctrl))
     # each job's sampled table is the pairs its candidates can reach: it must keep the target pair
     # of a touching pose, and may drop every pair of a clear one (then the scan has nothing to
     # filter and reports fp64)
-    for i in range(0, n, 3):
+    for i in range(0, len(jobs), 3):
         cfg = jobs[i].config()
         assert 0 <= cfg["sampled_pairs"] <= 12 and cfg["pair_order"] == "hit"
         assert cfg["scan"] == ("fp32-filtered" if cfg["sampled_pairs"] else "fp64")
