@@ -184,6 +184,52 @@ int sspp_scene_create(const sspp_model* m, int mode, int arg /* dof or body id *
 int sspp_scene_get_info(const sspp_scene* s, sspp_scene_info* out);
 void sspp_scene_free(sspp_scene* s);
 
+/* ---- re-posing a scene in place ----
+ * No reference counterpart: the reference's users hold the mjModel themselves and edit qpos0 /
+ * body_pos / body_quat between plans; here the scene keeps its own copy of the model's data
+ * (the sspp_model and other scenes of it are never touched) and these calls edit that copy.
+ *   sspp_scene_set_qpos       every free body's pose at once: qpos [nq] in the model's layout
+ *                             (pos, quat per free joint)
+ *   sspp_scene_set_body_pose  one body: a free-joint body -> its 7 qpos; a jointless body -> its
+ *                             pos / quat relative to its parent (mjModel.body_pos / body_quat);
+ *                             children follow
+ *   sspp_scene_get_qpos       the current values (quaternions normalised)
+ *   sspp_scene_epoch          0 at creation, +1 per successful update
+ * Quaternions are normalised as the MJCF loader normalises them.  A zero quaternion, a
+ * non-finite value, a wrong nq, body 0 or a bad body id is SSPP_E_INVAL, and the scene and its
+ * epoch stay as they were.  qpos entries of the scene's own moving bodies are not obstacles but
+ * the defaults of their undriven components; they update like the others.
+ *
+ * After a successful update every later call on every object bound to the scene (jobs, planners,
+ * the cached planner of sspp_plan_sspp, step executors, CES planners alone and in groups) returns,
+ * bit for bit, what fresh objects with the same arguments return on a scene created from a model
+ * holding the new values; sspp_scene_get_info's static_contacts / static_cost and the read-back
+ * options (SSPP_OPT_NPAIRS, _CYLBOX, _CAPSULE, _CYLCYL, _ORDER, _WP_ORDER, _PREPASS_STATE)
+ * describe the new tables.  Job options, seeds, a job's current query and query set, and a CES
+ * planner's distribution, forwarded best and iteration count are kept.
+ * Scan order: the update repeats what the job's creation did for its order — a job created by
+ * sspp_job_create_sspp with hit order runs the census again inside this call; a drop-in planner's
+ * job goes back to gap / bisection order (SSPP_OPT_ORDER 1, _WP_ORDER 0, _PREPASS_STATE 3) and
+ * restarts its asynchronous pre-pass at its second launch in the new world, which the first
+ * launch after it lands swaps in: the hit order is rebuilt only when several plans follow one
+ * update, and a loop of one plan per update pays no census.  The device buffers a pre-pass
+ * replaced are released by the next update, so a loop of updates holds a bounded number.
+ * Results are identical in every order.
+ * Errors other than SSPP_E_INVAL (a HIP failure while the tables are copied) can leave the scene
+ * and its jobs partly in the new world with the epoch unchanged: free the scene and its objects.
+ *
+ * Lifetime: host-synchronous, like sspp_scene_free.  The caller must have no launch in flight on
+ * its own streams that uses the scene, and must not call into the scene's objects from another
+ * thread meanwhile.  The call joins the running pre-passes of the scene's jobs (a result computed
+ * for the older world is never swapped in), waits for the device (so for the library's shared
+ * planner and pre-pass streams), then re-derives every table inside this call: the job run
+ * functions stay asynchronous, allocation-free and capturable afterwards.  A graph captured
+ * before an update holds the older tables' arguments and must be captured again. */
+int sspp_scene_set_qpos(sspp_scene* s, const double* qpos, int nq);
+int sspp_scene_set_body_pose(sspp_scene* s, int body, const double pos[3], const double quat[4]);
+int sspp_scene_get_qpos(const sspp_scene* s, double* qpos_out, int nq);
+int sspp_scene_epoch(const sspp_scene* s, int64_t* epoch);
+
 /* ---- splines (host) ---- */
 int sspp_interpolate(const double* pts /* [n][D] */, int n, int D, int degree,
                      const double* u /* [n] */, double* knots_out /* [n+degree+1] */,

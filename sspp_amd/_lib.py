@@ -110,6 +110,10 @@ SIGNATURES = {
     "sspp_scene_create": (C.c_int, [_vp, _i, _i, _i, C.POINTER(_vp)]),
     "sspp_scene_get_info": (C.c_int, [_vp, C.POINTER(SceneInfo)]),
     "sspp_scene_free": (None, [_vp]),
+    "sspp_scene_set_qpos": (C.c_int, [_vp, _d, _i]),
+    "sspp_scene_set_body_pose": (C.c_int, [_vp, _i, _d, _d]),
+    "sspp_scene_get_qpos": (C.c_int, [_vp, _d, _i]),
+    "sspp_scene_epoch": (C.c_int, [_vp, C.POINTER(_i64)]),
     "sspp_interpolate": (C.c_int, [_d, _i, _i, _i, _d, _d, _d]),
     "sspp_spline_eval": (C.c_int, [_d, _i, _i, _d, _i, C.c_double, _d]),
     "sspp_job_create_sspp": (C.c_int, [_vp, C.POINTER(SsppArgs), _i64, C.POINTER(_vp)]),

@@ -60,12 +60,7 @@ std::vector<double> floats(const std::string& s) {
     return v;
 }
 
-void normq(double* q) {
-    double s = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
-    double n = std::sqrt(s);
-    if (n > 0) { for (int k = 0; k < 4; ++k) q[k] = q[k] / n; }
-    else { q[0] = 1; q[1] = q[2] = q[3] = 0; }
-}
+void normq(double* q) { loader_normq(q); }  // (model.h: shared with scene updates)
 
 void qmul(const double* a, const double* b, double* r) {
     double t0 = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];

@@ -1,5 +1,6 @@
 // model.h — host-side scene model (MuJoCo-like flat arrays) and shared host helpers.
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -26,6 +27,15 @@ void clear_error();
 
 // MJCF -> model (mjcf.cpp)
 int load_mjcf(const std::string& path, sspp_model& out);
+// the loader's quaternion normalisation (body quat, qpos0): q / |q|, the identity for |q| = 0.  A
+// scene update (sspp_scene_set_qpos) normalises with the same operations, so that a re-posed
+// scene holds the bits a scene loaded from a file with those values holds
+inline void loader_normq(double* q) {
+    double s = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
+    double n = std::sqrt(s);
+    if (n > 0) { for (int k = 0; k < 4; ++k) q[k] = q[k] / n; }
+    else { q[0] = 1; q[1] = q[2] = q[3] = 0; }
+}
 
 // spline helpers (spline_host.cpp) — Eigen Splines semantics
 void knot_averaging(const double* u, int n, int p, double* knots);

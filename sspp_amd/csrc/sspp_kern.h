@@ -34,6 +34,7 @@
 #include <cstdlib>
 #include <cmath>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <thread>
 #include <type_traits>
@@ -2720,6 +2721,15 @@ struct sspp_scene {
     Dev<DMover> d_movers;
     Dev<DPair> d_visit;  // the pairs grouped by moving geom (SceneT::visit)
     int device = 0;
+    // re-posing (sspp_scene_set_qpos / _set_body_pose): the scene's own copy of the
+    // model (its qpos0 / body_pos / body_quat are the poses the tables above were built from), the
+    // moving bodies chosen at creation, the updates so far, and the jobs bound to this scene —
+    // an update joins their pre-passes and re-derives their tables
+    sspp_model model;
+    std::vector<int> mover_bodies;
+    int64_t epoch = 0;
+    mutable std::mutex jobs_mu;
+    mutable std::vector<sspp_job*> jobs;
 };
 
 // A pair table: the pairs one launch scans, in scan order, on the host and on the device, with what
@@ -2870,15 +2880,45 @@ struct sspp_job {
                                         // get-options that describe "the sampled table" read it
     Staging qst;                        // pinned source of the set's async copies, and the event
                                         // recorded after them: the next set waits on it
-    // wait for a running pre-pass and drop its result (option changes, the destructor)
+    // what a scene update (sspp_scene_set_qpos) repeats of this job's creation: the order it was
+    // created with or last set to (SSPP_OPT_ORDER), and whether the hit order comes from the
+    // asynchronous pre-pass (sspp::job_create_sspp_async) or from the synchronous census
+    int want_order = 0;
+    bool async_pre = false;
+    bool bound = false;                 // listed in scene->jobs (cleared when the scene dies first)
+    // launches to go before the asynchronous pre-pass restarts after a scene update (0: none
+    // pending): the second launch in the same world starts it, so a loop of one plan per update
+    // pays no census
+    int pre_wait = 0;
+    // wait for a running pre-pass and drop its result (option changes, scene updates, the destructor)
+    // (the thread gives up at its next stage once pre_stop is set: a scene update in a planning loop
+    // does not wait for an ordering nobody will use)
+    std::atomic<int> pre_stop{0};
     void prepass_drop() {
-        if (prepass_thread.joinable()) prepass_thread.join();
+        if (prepass_thread.joinable()) {
+            pre_stop.store(1, std::memory_order_relaxed);
+            prepass_thread.join();
+            pre_stop.store(0, std::memory_order_relaxed);
+        }
         prepass_state.store(3, std::memory_order_relaxed);
+    }
+    // the job into its scene's list, so that a scene update reaches it
+    void bind(const sspp_scene* s) {
+        scene = s;
+        if (!s) return;
+        std::lock_guard<std::mutex> g(s->jobs_mu);
+        s->jobs.push_back(this);
+        bound = true;
     }
     // the thread and the pre-pass stream use the members: both are done before any member dies
     ~sspp_job() {
         prepass_drop();
         if (pre_stream) (void)hipStreamSynchronize(pre_stream);
+        if (bound && scene) {
+            std::lock_guard<std::mutex> g(scene->jobs_mu);
+            auto it = std::find(scene->jobs.begin(), scene->jobs.end(), this);
+            if (it != scene->jobs.end()) scene->jobs.erase(it);
+        }
     }
 };
 

@@ -7,6 +7,7 @@
 // prepass_apply, sspp_job_set_queries) and run_sspp hands a launch the one launch_table picks.
 // Device buffers, pinned memory and events are members of the owning types of sspp_own.h.
 #include "sspp_kern.h"
+#include "sspp_scene_build.h"
 
 #include <chrono>
 #include <random>
@@ -65,59 +66,38 @@ __global__ __launch_bounds__(kArgminThreads) void k_argmin(const BlockBest* __re
 }  // namespace sspk
 
 // =============================================================== host side: scene + jobs
-namespace {
 
-// MuJoCo-like kinematics on the host (same operation order as oracle/sspp_oracle.c::fk)
-void host_fk(const sspp_model& m, const std::vector<double>& qpos, std::vector<double>& xpos,
-             std::vector<double>& xquat, std::vector<double>& xmat, std::vector<double>& gxpos,
-             std::vector<double>& gxmat) {
-    int nb = m.nbody(), ng = m.ngeom();
-    xpos.assign(3 * nb, 0.0); xquat.assign(4 * nb, 0.0); xmat.assign(9 * nb, 0.0);
-    gxpos.assign(3 * ng, 0.0); gxmat.assign(9 * ng, 0.0);
-    xquat[0] = 1.0;
-    quat2mat(&xquat[0], &xmat[0]);
-    for (int b = 1; b < nb; ++b) {
-        double* p = &xpos[3 * b];
-        double* q = &xquat[4 * b];
-        if (m.body_jnt_type[b] == 0) {
-            const double* qp = &qpos[m.body_qpos_adr[b]];
-            p[0] = qp[0]; p[1] = qp[1]; p[2] = qp[2];
-            q[0] = qp[3]; q[1] = qp[4]; q[2] = qp[5]; q[3] = qp[6];
-        } else {
-            int pa = m.body_parent[b];
-            double t[3];
-            matvec3(&xmat[9 * pa], &m.body_pos[3 * b], t);
-            p[0] = xpos[3 * pa] + t[0]; p[1] = xpos[3 * pa + 1] + t[1]; p[2] = xpos[3 * pa + 2] + t[2];
-            mulquat(&xquat[4 * pa], &m.body_quat[4 * b], q);
-        }
-        normalize4(q);
-        quat2mat(q, &xmat[9 * b]);
+// The tables sspb::scene_build made, into the scene and its device buffers (synchronous copies;
+// the caller has made sure no launch still reads them).  A pose update changes no table's length
+// (the pair filter does not look at poses), so every device buffer keeps its allocation.
+static int scene_adopt(sspp_scene* s, sspb::SceneTables&& t, bool create) {
+    if (!create) {
+        assert(t.geoms.size() == s->geoms.size() && t.pairs.size() == s->pairs.size() &&
+               t.movers.size() == s->movers.size() && t.visit.size() == s->d_visit.n);
+        if (t.geoms.size() != s->geoms.size() || t.pairs.size() != s->pairs.size() || t.movers.size() != s->movers.size())
+            return sspp::set_error(SSPP_E_SCENE, "scene update: a table changed its length");
     }
-    for (int g = 0; g < ng; ++g) {
-        int b = m.geom_body[g];
-        double t[3], gq[4];
-        matvec3(&xmat[9 * b], &m.geom_pos[3 * g], t);
-        gxpos[3 * g] = xpos[3 * b] + t[0];
-        gxpos[3 * g + 1] = xpos[3 * b + 1] + t[1];
-        gxpos[3 * g + 2] = xpos[3 * b + 2] + t[2];
-        mulquat(&xquat[4 * b], &m.geom_quat[4 * g], gq);
-        normalize4(gq);
-        quat2mat(gq, &gxmat[9 * g]);
-    }
+    s->geoms = std::move(t.geoms);
+    s->pairs = std::move(t.pairs);
+    s->movers = std::move(t.movers);
+    s->n_moving_geoms = t.n_moving_geoms; s->n_static_geoms = t.n_static_geoms;
+    s->n_static_pairs = t.n_static_pairs; s->static_contacts = t.static_contacts;
+    s->static_cost = t.static_cost;
+    int rc;
+    if ((rc = s->d_geoms.upload(s->geoms.data(), s->geoms.size())) ||
+        (rc = s->d_pairs.upload(s->pairs.data(), s->pairs.size())) ||
+        (rc = s->d_movers.upload(s->movers.data(), s->movers.size())) ||
+        (rc = s->d_visit.upload(t.visit.data(), t.visit.size())))
+        return rc;
+    return SSPP_OK;
 }
-
-}  // namespace
 
 extern "C" {
 
 int sspp_scene_create(const sspp_model* m, int mode, int arg, int count_static, sspp_scene** out) {
     sspp::clear_error();
     if (!m || !out) return sspp::set_error(SSPP_E_INVAL, "sspp_scene_create: null argument");
-    const int nb = m->nbody(), ng = m->ngeom();
-    std::vector<int> weld(nb, 0), moving(nb, 0);
-    for (int b = 1; b < nb; ++b)
-        weld[b] = (m->body_jnt_type[b] != -1) ? b : weld[m->body_parent[b]];
-    std::vector<int> mover_of(nb, -1);
+    const int nb = m->nbody();
     std::vector<int> mover_bodies;
     if (mode == SSPP_MODE_QPOS) {
         if (arg < 1 || arg > 16) return sspp::set_error(SSPP_E_INVAL, "dof must be in [1, 16]");
@@ -125,16 +105,10 @@ int sspp_scene_create(const sspp_model* m, int mode, int arg, int count_static, 
             return sspp::set_error(SSPP_E_SCENE, "model has nq=" + std::to_string(m->qpos0.size()) +
                                                      " < dof=" + std::to_string(arg));
         for (int b = 1; b < nb; ++b)
-            if (m->body_jnt_type[b] == 0 && m->body_qpos_adr[b] < arg) {
-                moving[b] = 1;
-                mover_of[b] = (int)mover_bodies.size();
-                mover_bodies.push_back(b);
-            }
+            if (m->body_jnt_type[b] == 0 && m->body_qpos_adr[b] < arg) mover_bodies.push_back(b);
     } else if (mode == SSPP_MODE_BODY) {
         if (arg <= 0 || arg >= nb || m->body_jnt_type[arg] != 0)
             return sspp::set_error(SSPP_E_SCENE, "collision body must have a free joint");
-        moving[arg] = 1;
-        mover_of[arg] = 0;
         mover_bodies.push_back(arg);
     } else {
         return sspp::set_error(SSPP_E_INVAL, "unknown scene mode");
@@ -145,165 +119,39 @@ int sspp_scene_create(const sspp_model* m, int mode, int arg, int count_static, 
         if (mode == SSPP_MODE_QPOS && m->body_qpos_adr[mover_bodies[i]] != 7 * (int)i)
             return sspp::set_error(SSPP_E_UNSUPPORTED, "free joints must occupy qpos[7k:7k+7]");
 
+    // everything from here on is a function of (model data, poses, mode, moving bodies): the
+    // same code a pose update runs (scene_repose)
+    sspb::SceneTables t;
+    int rc = sspb::scene_build(*m, mode, mover_bodies, t);
+    if (rc) return rc;
     auto* s = new sspp_scene();
     s->mode = mode; s->arg = arg; s->dof = mode == SSPP_MODE_QPOS ? arg : 4;
     s->count_static = count_static;
     (void)hipGetDevice(&s->device);
-
-    // kinematics at qpos0: world poses of static geoms
-    std::vector<double> xpos, xquat, xmat, gxpos, gxmat;
-    host_fk(*m, m->qpos0, xpos, xquat, xmat, gxpos, gxmat);
-    // moving geoms relative to their mover root: same FK with every mover at the identity
-    std::vector<double> qrel = m->qpos0;
-    for (int b : mover_bodies) {
-        int adr = m->body_qpos_adr[b];
-        double id[7] = {0, 0, 0, 1, 0, 0, 0};
-        for (int k = 0; k < 7; ++k) qrel[adr + k] = id[k];
-    }
-    std::vector<double> rxpos, rxquat, rxmat, rgxpos, rgxmat;
-    host_fk(*m, qrel, rxpos, rxquat, rxmat, rgxpos, rgxmat);
-
-    std::vector<int> table_index(ng, -1);
-    for (int g = 0; g < ng; ++g) {
-        int b = m->geom_body[g];
-        int w = weld[b];
-        bool mv = moving[w];
-        DGeom dg{};
-        dg.type = m->geom_type[g];
-        dg.mover = mv ? mover_of[w] : -1;
-        dg.orig = g;
-        const std::vector<double>& P = mv ? rgxpos : gxpos;
-        const std::vector<double>& M = mv ? rgxmat : gxmat;
-        for (int k = 0; k < 3; ++k) dg.pos[k] = P[3 * g + k];
-        for (int k = 0; k < 9; ++k) dg.mat[k] = M[9 * g + k];
-        for (int k = 0; k < 3; ++k) dg.size[k] = m->geom_size[3 * g + k];
-        dg.rbound = geom_rbound(dg.type, dg.size);
-        dg.relrot = 0;
-        for (int k = 0; k < 9; ++k) dg.relrot |= dg.mat[k] != ((k % 4 == 0) ? 1.0 : 0.0);
-        dg.reach = mv ? std::sqrt(dg.pos[0] * dg.pos[0] + dg.pos[1] * dg.pos[1] + dg.pos[2] * dg.pos[2]) * (1.0 + 1e-12)
-                      : 0.0;
-        fill_f32(dg);
-        table_index[g] = (int)s->geoms.size();
-        s->geoms.push_back(dg);
-        if (m->geom_contype[g] || m->geom_conaffinity[g]) {
-            if (mv) s->n_moving_geoms++; else s->n_static_geoms++;
-        }
-    }
-    // mj_collision pair filter, (g1 < g2) order
-    struct P2 { int g1, g2; double margin; bool stat; };
-    std::vector<P2> all;
-    for (int g1 = 0; g1 < ng; ++g1) {
-        for (int g2 = g1 + 1; g2 < ng; ++g2) {
-            int b1 = m->geom_body[g1], b2 = m->geom_body[g2];
-            int w1 = weld[b1], w2 = weld[b2];
-            if (w1 == w2) continue;
-            int ct1 = m->geom_contype[g1], ca1 = m->geom_conaffinity[g1];
-            int ct2 = m->geom_contype[g2], ca2 = m->geom_conaffinity[g2];
-            if (!((ct1 & ca2) || (ct2 & ca1))) continue;
-            if (w1 != 0 && w2 != 0 &&
-                (w1 == weld[m->body_parent[w2]] || w2 == weld[m->body_parent[w1]]))
-                continue;
-            bool excl = false;
-            for (size_t e = 0; e + 1 < m->exclude.size(); e += 2) {
-                int e1 = m->exclude[e], e2 = m->exclude[e + 1];
-                if ((e1 == b1 && e2 == b2) || (e1 == b2 && e2 == b1)) { excl = true; break; }
-            }
-            if (excl) continue;
-            if (!pair_supported(m->geom_type[g1], m->geom_type[g2])) {
-                delete s;
-                return sspp::set_error(SSPP_E_UNSUPPORTED,
-                                       "unsupported collision pair: geom '" + m->geom_names[g1] +
-                                           "' (type " + std::to_string(m->geom_type[g1]) + ") vs '" +
-                                           m->geom_names[g2] + "' (type " +
-                                           std::to_string(m->geom_type[g2]) + ")");
-            }
-            double mg = std::max(m->geom_margin[g1], m->geom_margin[g2]);
-            all.push_back({g1, g2, mg, !(moving[w1] || moving[w2])});
-        }
-    }
-    // env-env pairs: constant over waypoints -> evaluated once here (same device math)
-    for (auto& pr : all) {
-        if (!pr.stat) continue;
-        s->n_static_pairs++;
-        const DGeom& A = s->geoms[table_index[pr.g1]];
-        const DGeom& B = s->geoms[table_index[pr.g2]];
-        double dc[3] = {B.pos[0] - A.pos[0], B.pos[1] - A.pos[1], B.pos[2] - A.pos[2]};
-        if (A.rbound > 0.0 && B.rbound > 0.0) {
-            double thr = A.rbound + B.rbound + pr.margin;
-            if (dot3(dc, dc) > thr * thr) continue;
-        }
-        bool afirst = A.type <= B.type;
-        const DGeom& F = afirst ? A : B;
-        const DGeom& S = afirst ? B : A;
-        int nd = 0;
-        int nc = collide<false>(F.type, F.pos, F.mat, F.size, S.type, S.pos, S.mat, S.size, pr.margin, &nd);
-        collide<true>(F.type, F.pos, F.mat, F.size, S.type, S.pos, S.mat, S.size, pr.margin, &nd);
-        s->static_contacts += nc;
-        if (nd > 0) {
-            double term = -1.0 / (sqrt(dot3(dc, dc)) + 1e-4);
-            for (int i = 0; i < nd; ++i) s->static_cost = s->static_cost + term;
-        }
-    }
-    // moving pairs: sspp mode groups by moving geom (pose computed once per group);
-    // tsp mode keeps the oracle's (g1, g2) order so per-waypoint cost sums match bit for bit.
-    std::vector<P2> mov;
-    for (auto& pr : all)
-        if (!pr.stat) mov.push_back(pr);
-    auto moving_geom = [&](const P2& pr) {
-        int w1 = weld[m->geom_body[pr.g1]];
-        return moving[w1] ? pr.g1 : pr.g2;
-    };
-    if (mode == SSPP_MODE_QPOS) {
-        std::stable_sort(mov.begin(), mov.end(), [&](const P2& x, const P2& y) {
-            return moving_geom(x) < moving_geom(y);
-        });
-    }
-    for (auto& pr : mov) {
-        int gm = moving_geom(pr);
-        int go = gm == pr.g1 ? pr.g2 : pr.g1;
-        DPair dp{};
-        dp.gm = table_index[gm];
-        dp.go = table_index[go];
-        const DGeom& O = s->geoms[dp.go];
-        dp.otype = O.type;
-        dp.oorig = O.orig;
-        dp.omover = O.mover;
-        dp.margin = pr.margin;
-        for (int k = 0; k < 3; ++k) dp.opos[k] = O.pos[k];
-        for (int k = 0; k < 9; ++k) dp.omat[k] = O.mat[k];
-        for (int k = 0; k < 3; ++k) dp.osize[k] = O.size[k];
-        dp.orbound = O.rbound;
-        fill_f32(dp);
-        s->pairs.push_back(dp);
-    }
-    for (size_t i = 0; i < mover_bodies.size(); ++i) {
-        DMover mv{};
-        mv.qpos_adr = m->body_qpos_adr[mover_bodies[i]];
-        for (int k = 0; k < 7; ++k) mv.qpos0[k] = m->qpos0[mv.qpos_adr + k];
-        s->movers.push_back(mv);
-    }
-    // the pair visit order of the record-form pair loops (SceneT::visit): grouped by moving geom,
-    // the reference's order within a group; only for tables a mask word can cover
-    std::vector<DPair> visit;
-    if (!s->pairs.empty() && s->pairs.size() <= 64) {
-        std::vector<int> ix(s->pairs.size());
-        for (size_t i = 0; i < ix.size(); ++i) ix[i] = (int)i;
-        std::stable_sort(ix.begin(), ix.end(), [&](int x, int y) { return s->pairs[x].gm < s->pairs[y].gm; });
-        for (int i : ix) {
-            DPair q = s->pairs[i];
-            q.pad = i;  // its record index
-            visit.push_back(q);
-        }
-    }
-    int rc;
-    if ((rc = s->d_geoms.upload(s->geoms.data(), s->geoms.size())) ||
-        (rc = s->d_pairs.upload(s->pairs.data(), s->pairs.size())) ||
-        (rc = s->d_movers.upload(s->movers.data(), s->movers.size())) ||
-        (rc = s->d_visit.upload(visit.data(), visit.size()))) {
+    s->model = *m;  // the scene's own copy: updates edit it, never the caller's model
+    s->mover_bodies = mover_bodies;
+    if ((rc = scene_adopt(s, std::move(t), true))) {
         sspp_scene_free(s);
         return rc;
     }
     *out = s;
+    return SSPP_OK;
+}
+
+int sspp_scene_get_qpos(const sspp_scene* s, double* qpos_out, int nq) {
+    sspp::clear_error();
+    if (!s || !qpos_out) return sspp::set_error(SSPP_E_INVAL, "sspp_scene_get_qpos: null argument");
+    if (nq != (int)s->model.qpos0.size())
+        return sspp::set_error(SSPP_E_INVAL, "sspp_scene_get_qpos: nq = " + std::to_string(nq) + ", the model has " +
+                                                 std::to_string(s->model.qpos0.size()));
+    std::copy(s->model.qpos0.begin(), s->model.qpos0.end(), qpos_out);
+    return SSPP_OK;
+}
+
+int sspp_scene_epoch(const sspp_scene* s, int64_t* epoch) {
+    sspp::clear_error();
+    if (!s || !epoch) return sspp::set_error(SSPP_E_INVAL, "sspp_scene_epoch: null argument");
+    *epoch = s->epoch;
     return SSPP_OK;
 }
 
@@ -322,6 +170,11 @@ int sspp_scene_get_info(const sspp_scene* s, sspp_scene_info* out) {
 void sspp_scene_free(sspp_scene* s) {
     if (!s) return;
     sspp::planner_cache_drop(s);
+    {  // a job that outlives its scene must not look for the scene's list when it dies
+        std::lock_guard<std::mutex> g(s->jobs_mu);
+        for (sspp_job* j : s->jobs) j->bound = false;
+        s->jobs.clear();
+    }
     delete s;
 }
 
@@ -428,7 +281,11 @@ static std::vector<int> c2f_order(int W) {
 // waypoint that settles the most candidates not yet settled (up to kPick in all), the rest in
 // bisection order.
 constexpr int kCensus = 2048, kPick = 12;
-static void waypoints_from_census(const std::vector<uint64_t>& hits, int M, int W, int n1, std::vector<int>& wps) {
+// stop (optional): set by a job that drops its pre-pass; the ordering then returns early, its
+// result unused
+static void waypoints_from_census(const std::vector<uint64_t>& hits, int M, int W, int n1, std::vector<int>& wps,
+                                  const std::atomic<int>* stop = nullptr) {
+    auto stopped = [&] { return stop && stop->load(std::memory_order_relaxed) != 0; };
     const int nw = (W + 64) >> 6, npts = W + 1, mw = (M + 63) / 64;
     // per waypoint: the candidates in contact there, as bits
     std::vector<uint64_t> col((size_t)npts * mw, 0ull);
@@ -448,6 +305,7 @@ static void waypoints_from_census(const std::vector<uint64_t>& hits, int M, int 
     n1 = std::max(1, std::min(n1, npts));
     std::vector<int> S;
     for (int r = 0; r < n1; ++r) {  // greedy
+        if (stopped()) return;
         int bi = -1, bc = M + 1;
         for (int i = 0; i < npts; ++i) {
             if (std::find(S.begin(), S.end(), i) != S.end()) continue;
@@ -460,6 +318,7 @@ static void waypoints_from_census(const std::vector<uint64_t>& hits, int M, int 
     }
     int cur = untouched(S);
     for (int pass = 0; pass < 16; ++pass) {  // single swaps
+        if (stopped()) return;
         int bpos = -1, bi = -1, bc = cur;
         for (int pos = 0; pos < n1; ++pos) {
             const int keep = S[pos];
@@ -477,6 +336,7 @@ static void waypoints_from_census(const std::vector<uint64_t>& hits, int M, int 
     }
     std::vector<int> order = S;
     while ((int)order.size() < kPick && (int)order.size() < npts) {  // greedy continuation
+        if (stopped()) return;
         int bi = -1, bc = untouched(order);
         for (int i = 0; i < npts; ++i) {
             if (std::find(order.begin(), order.end(), i) != order.end()) continue;
@@ -499,7 +359,7 @@ static void waypoints_from_census(const std::vector<uint64_t>& hits, int M, int 
 // yet settled, the rest in their previous order.
 static void pairs_by_hits(const sspp_scene* sc, std::vector<DPair>& pairs, const double* knots, int nknots, int p,
                           const double* ctrl0, int D, double sigma, const double* limits, int W,
-                          const std::vector<int>& pick) {
+                          const std::vector<int>& pick, const std::atomic<int>* stop = nullptr) {
     const int np = (int)pairs.size(), n = nknots - p - 1, nm = (int)sc->movers.size();
     if (np < 2 || np > 64 || nm < 1 || nm > kMaxMovers || pick.empty()) return;
     constexpr int M = 256;
@@ -508,6 +368,7 @@ static void pairs_by_hits(const sspp_scene* sc, std::vector<DPair>& pairs, const
     std::vector<uint64_t> cand(M, 0ull);
     std::vector<double> c((size_t)n * D);
     for (int m = 0; m < M; ++m) {
+        if (stop && stop->load(std::memory_order_relaxed)) return;  // (dropped: the order is not used)
         for (size_t e = 0; e < c.size(); ++e) c[e] = ctrl0[e];
         for (int jj = p; jj < n - p; ++jj)
             for (int d = 0; d < D; ++d) c[(size_t)jj * D + d] += sigma * N01(rng) * limits[d];
@@ -787,12 +648,23 @@ static int prepass_start(sspp_job* j, const double* init_ctrl, double sigma, con
             j->prepass_state.store(3, std::memory_order_release);
             return;
         }
+        // a dropped pre-pass (prepass_drop: an option change, a scene update, the job's end) gives
+        // up at the next stage; nothing of it is published
+        const std::atomic<int>* stop = &j->pre_stop;
+        auto dropped = [&] {
+            if (!stop->load(std::memory_order_relaxed)) return false;
+            j->prepass_state.store(3, std::memory_order_release);
+            return true;
+        };
+        if (dropped()) return;
         std::vector<uint64_t> hits(j->h_hits.p, j->h_hits.p + nh);
         std::vector<int> wps = c2f_order(j->W);
-        waypoints_from_census(hits, M, j->W, kThroughputG1, wps);
+        waypoints_from_census(hits, M, j->W, kThroughputG1, wps, stop);
+        if (dropped()) return;
         const std::vector<int> pick(wps.begin(), wps.begin() + std::min<size_t>(wps.size(), kThroughputG1));
         pairs_by_hits(sc, c.pairs, c.knots.data(), j->nknots, j->p, c.init.data(), j->D, c.sigma, c.limits.data(), j->W,
-                      pick);
+                      pick, stop);
+        if (dropped()) return;
         table_set(j->pre[kPairsSampled], sc,
                   reachable_pairs(sc, c.pairs, c.init.data(), j->n, j->D, j->p, c.sigma, c.limits.data(), j->sampler));
         table_set(j->pre[kPairsFull], sc, std::move(c.pairs));
@@ -873,7 +745,7 @@ static int job_create_sspp_impl(const sspp_scene* scene, const sspp_sspp_args* a
     if (scene && (scene->mode != SSPP_MODE_QPOS || scene->dof != D))
         return sspp::set_error(SSPP_E_INVAL, "scene was not bound for this dof");
     auto* j = new sspp_job();
-    j->kind = 0; j->scene = scene; j->D = D; j->p = p; j->n = n; j->W = W;
+    j->kind = 0; j->bind(scene); j->D = D; j->p = p; j->n = n; j->W = W;
     j->nknots = n + p + 1; j->sigma = a->sigma; j->seed = a->seed; j->max_batch = max_batch;
     j->arc_all = a->arc_all ? 1 : 0;
     j->sampler = a->sampler ? 1 : 0;
@@ -903,6 +775,8 @@ static int job_create_sspp_impl(const sspp_scene* scene, const sspp_sspp_args* a
     j->h_stage.insert(j->h_stage.end(), a->limits, a->limits + D);
     // hit order only for jobs that sample (sigma > 0): a scoring job's candidates are the caller's
     const int order = a->sigma != 0.0 ? 2 : 1;
+    j->want_order = order;
+    j->async_pre = async_prepass;
     if ((rc = set_job_tables(j, a->init_ctrl, a->sigma, a->limits, async_prepass ? 1 : order, true, nullptr)) ||
         (async_prepass && order == 2 && (rc = prepass_start(j, a->init_ctrl, a->sigma, a->limits)))) {
         sspp_job_free(j);
@@ -980,6 +854,12 @@ static int run_sspp(sspp_job* j, const double* d_ctrl, int64_t first_id, int64_t
         return sspp::set_error(SSPP_E_INVAL, "steps per launch: 1..64 (sampled candidates)");
     hipStream_t st = (hipStream_t)stream;
     if (j->prepass_state.load(std::memory_order_relaxed) == 2) prepass_apply(j);
+    // a drop-in planner's job after a scene update: the second launch in the new world restarts
+    // the hit-order pre-pass (a failure leaves the job in gap / bisection order)
+    if (j->pre_wait > 0 && --j->pre_wait == 0) {
+        const double* init = j->h_stage.data();
+        if (prepass_start(j, init, j->sigma, init + (size_t)j->n * j->D) != SSPP_OK) sspp::clear_error();
+    }
     int nt, g1;
     c2f_shape(j, (int64_t)steps * B, &nt, &g1);
     const int n = j->n, D = j->D, p = j->p;
@@ -1114,6 +994,18 @@ extern "C" int sspp_job_update_sspp(sspp_job* j, const double* init_ctrl, double
     return j->upd.record(st);
 }
 
+// the pair table of a query set: the job's current table without the pairs no query can reach
+static std::vector<DPair> query_set_pairs(const sspp_job* j, int Q, const double* init_ctrl, const double* sigma,
+                                          const double* limits) {
+    const sspp_scene* sc = j->scene;
+    const size_t nd = (size_t)j->n * j->D, D = (size_t)j->D;
+    std::vector<ReachBox> lo((size_t)Q), hi((size_t)Q);
+    for (int q = 0; q < Q; ++q)
+        reach_box(sc, init_ctrl + q * nd, j->n, j->D, j->p, sigma[q], limits + q * D, j->sampler, lo[q].v, hi[q].v);
+    const std::vector<DPair>& full = j->tab[kPairsFull].h;
+    return pairs_in_boxes(sc, full.empty() ? sc->pairs : full, lo.data(), hi.data(), Q);
+}
+
 // A query set for query launches: Q independent queries (initial spline, sigma, limits, seed each)
 // against this job's scene, knots and check_points.  Their values go to the job's query tables
 // (asynchronous, from job-owned pinned staging: valid until the next set), and the set's pair
@@ -1145,15 +1037,7 @@ extern "C" int sspp_job_set_queries(sspp_job* j, int Q, const double* init_ctrl,
     std::memcpy(hv + Q * (nd + D), sigma, sizeof(double) * Q);
     std::memcpy(hv + Q * (nd + D + 1), seed, sizeof(uint64_t) * Q);
     HIPCHK(hipMemcpyAsync(j->d_qtab.p, hv, sizeof(double) * nv, hipMemcpyHostToDevice, st));
-    std::vector<DPair> reach;
-    if (pairs) {
-        std::vector<ReachBox> lo((size_t)Q), hi((size_t)Q);
-        for (int q = 0; q < Q; ++q)
-            reach_box(sc, init_ctrl + q * nd, j->n, j->D, j->p, sigma[q], limits + q * D, j->sampler, lo[q].v, hi[q].v);
-        const std::vector<DPair>& full = j->tab[kPairsFull].h;
-        reach = pairs_in_boxes(sc, full.empty() ? sc->pairs : full, lo.data(), hi.data(), Q);
-    }
-    table_set(tq, sc, std::move(reach));
+    table_set(tq, sc, pairs ? query_set_pairs(j, Q, init_ctrl, sigma, limits) : std::vector<DPair>());
     if (!tq.h.empty()) {
         unsigned char* pp = j->qst.buf.p + vcap;
         std::memcpy(pp, tq.h.data(), sizeof(DPair) * tq.h.size());
@@ -1172,6 +1056,80 @@ extern "C" int sspp_job_sample_score_queries(sspp_job* j, int64_t first_id, int6
                                              uint8_t* d_feasible, double* d_ctrl_out, sspp_best* d_best,
                                              void* stream) {
     return run_sspp(j, nullptr, first_id, B, d_arc, d_feasible, d_ctrl_out, d_best, stream, 1, 0, true);
+}
+
+// ---------------------------------------------------------------- scene updates
+// A SamplingPathPlanner job after its scene's poses changed: what its creation did, again, for
+// the values it holds now (h_stage: the last update's initial spline and limits) — gap order and
+// the reachable subset from the new pairs, then the hit order by the synchronous census, or by the
+// asynchronous pre-pass for a drop-in planner's job; the query set's table from its staged
+// values.  The device is idle (scene_repose), so every copy is synchronous and the device tables
+// keep their allocations (room for every pair of the scene).  TaskSpacePlanner jobs derive their
+// launch's flags from the scene at each launch and hold no table: nothing to do.
+static int job_follow_scene(sspp_job* j) {
+    const sspp_scene* sc = j->scene;
+    if (j->kind != 0 || !sc || sc->pairs.empty()) return SSPP_OK;
+    const size_t nd = (size_t)j->n * j->D;
+    const double *init = j->h_stage.data(), *limits = init + nd;
+    ++j->tables_gen;
+    const bool hit = j->want_order == 2;
+    const int view_q = j->view_q;  // (which sampled table the read-backs describe: unchanged)
+    int rc = set_job_tables(j, init, j->sigma, limits, hit && j->async_pre ? 1 : j->want_order, true, nullptr);
+    if (rc) return rc;
+    j->pre_wait = hit && j->async_pre ? 2 : 0;  // (run_sspp: the second launch in this world restarts the pre-pass)
+    // the device is idle: what earlier pre-passes replaced is free to go, so a loop of updates
+    // holds at most one pre-pass's replaced buffers
+    j->retired.bufs.clear();
+    if (j->nq > 0) {  // the set's values: init [Q][n][D] | limits [Q][D] | sigma [Q] in the staging
+        const size_t Q = (size_t)j->nq;
+        const double* hv = (const double*)j->qst.buf.p;
+        PairTable& tq = j->tab[kPairsQueries];
+        table_set(tq, sc, query_set_pairs(j, j->nq, hv, hv + Q * (nd + j->D), hv + Q * nd));
+        if (!tq.h.empty())
+            HIPCHK(hipMemcpy(tq.d.p, tq.h.data(), sizeof(DPair) * tq.h.size(), hipMemcpyHostToDevice));
+    }
+    j->view_q = view_q;
+    return SSPP_OK;
+}
+
+// The scene to the poses of `trial` (a copy of its model data with new qpos0 / body_pos /
+// body_quat).  Nothing is touched before the new tables exist; then the pre-passes of the
+// scene's jobs are joined and dropped (their threads read scene->geoms), the device is drained,
+// and the scene and every job bound to it are rebuilt by the code that created them.
+static int scene_repose(sspp_scene* s, sspp_model&& trial) {
+    sspb::SceneTables t;
+    int rc = sspb::scene_build(trial, s->mode, s->mover_bodies, t);
+    if (rc) return rc;
+    std::vector<sspp_job*> jobs;
+    {
+        std::lock_guard<std::mutex> g(s->jobs_mu);
+        jobs = s->jobs;
+    }
+    for (sspp_job* j : jobs)  // (a job that never started one keeps SSPP_OPT_PREPASS_STATE 0, as a fresh job)
+        if (j->prepass_state.load(std::memory_order_acquire) != 0) j->prepass_drop();
+    HIPCHK(hipDeviceSynchronize());
+    s->model = std::move(trial);
+    if ((rc = scene_adopt(s, std::move(t), false))) return rc;
+    for (sspp_job* j : jobs)
+        if ((rc = job_follow_scene(j))) return rc;
+    ++s->epoch;
+    return SSPP_OK;
+}
+
+extern "C" int sspp_scene_set_qpos(sspp_scene* s, const double* qpos, int nq) {
+    sspp::clear_error();
+    if (!s) return sspp::set_error(SSPP_E_INVAL, "sspp_scene_set_qpos: null scene");
+    sspp_model trial = s->model;
+    if (int rc = sspb::model_set_qpos(trial, qpos, nq)) return rc;
+    return scene_repose(s, std::move(trial));
+}
+
+extern "C" int sspp_scene_set_body_pose(sspp_scene* s, int body, const double pos[3], const double quat[4]) {
+    sspp::clear_error();
+    if (!s) return sspp::set_error(SSPP_E_INVAL, "sspp_scene_set_body_pose: null scene");
+    sspp_model trial = s->model;
+    if (int rc = sspb::model_set_body_pose(trial, body, pos, quat)) return rc;
+    return scene_repose(s, std::move(trial));
 }
 
 extern "C" int sspp_job_score_ctrl(sspp_job* j, const double* d_ctrl, int64_t first_id, int64_t B,
@@ -1199,6 +1157,9 @@ extern "C" int sspp_job_set_option(sspp_job* j, int key, int64_t value) {
             if (j->kind != 0 || value < 0 || value > 2) return sspp::set_error(SSPP_E_INVAL, "SSPP_OPT_ORDER: 0, 1 or 2");
             j->prepass_drop();
             HIPCHK(hipDeviceSynchronize());  // earlier launches may still read the tables
+            j->want_order = (int)value;  // (a scene update repeats this order, synchronously)
+            j->async_pre = false;
+            j->pre_wait = 0;
             const size_t nd = (size_t)j->n * j->D;
             return set_job_tables(j, j->h_stage.data(), j->sigma, j->h_stage.data() + nd, (int)value, true, nullptr);
         }
@@ -1296,7 +1257,7 @@ extern "C" int sspp_job_create_tsp(const sspp_scene* scene, const sspp_tsp_args*
     if (max_batch < 1) return sspp::set_error(SSPP_E_INVAL, "max_batch must be >= 1");
     if (n < 3) return sspp::set_error(SSPP_E_INVAL, "degree-2 interpolation needs >= 3 points");
     auto* j = new sspp_job();
-    j->kind = 1; j->scene = scene; j->D = 4; j->p = 2; j->n = n; j->K = K; j->cp = cp;
+    j->kind = 1; j->bind(scene); j->D = 4; j->p = 2; j->n = n; j->K = K; j->cp = cp;
     j->nknots = n + 3; j->seed = a->seed; j->max_batch = max_batch; j->nm = 1;
     for (int i = 0; i < 4; ++i) { j->start[i] = a->start[i]; j->end[i] = a->end[i]; j->lo[i] = a->lo[i]; j->hi[i] = a->hi[i]; }
     j->z_min = a->z_min; j->w_col = a->w_collision;

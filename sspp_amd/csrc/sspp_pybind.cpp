@@ -317,6 +317,43 @@ public:
                                    path_.ctrl.data(), self);
     }
 
+    // Re-posing the scene in place (sspp_scene_set_qpos / _set_body_pose; not the reference's API,
+    // whose users edit their own mjModel): every later call plans in the new world, as a fresh
+    // planner on an XML with those values would.  plan()'s own state (get_ctrl_pts, last_best_*,
+    // last_feasible_ids) is left as it was.
+    void set_qpos(py::array_t<double, py::array::forcecast> qpos) {
+        py::array_t<double> c = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(qpos);
+        auto lk = lock();
+        ensure_scene();
+        ck(sspp_scene_set_qpos(scene_.get(), c.data(), (int)c.size()), "set_qpos");
+    }
+    void set_body_pose(const std::string& name, py::array_t<double, py::array::forcecast> pos,
+                       py::array_t<double, py::array::forcecast> quat) {
+        auto p = vec_of(pos, 3, "pos"), q = vec_of(quat, 4, "quat");
+        const int body = sspp_model_body_id(model_.get(), name.c_str());
+        ck(body, "set_body_pose");
+        auto lk = lock();
+        ensure_scene();
+        ck(sspp_scene_set_body_pose(scene_.get(), body, p.data(), q.data()), "set_body_pose");
+    }
+    py::array_t<double> get_qpos() {
+        auto lk = lock();
+        ensure_scene();
+        sspp_model_view v{};
+        ck(sspp_model_view_get(model_.get(), &v), "get_qpos");
+        py::array_t<double> out((ssize_t)v.nq);
+        ck(sspp_scene_get_qpos(scene_.get(), out.mutable_data(), v.nq), "get_qpos");
+        return out;
+    }
+    // diagnostics: a read-back option (SSPP_OPT_*) of the last plan() shape's job
+    int64_t option(int key) {
+        auto lk = lock();
+        ensure_planner();
+        int64_t v = 0;
+        ck(sspp_planner_get_option(planner_.get(), key, &v), "option");
+        return v;
+    }
+
     uint64_t seed = 0x5EED;
     double last_best_cost = INFINITY;
     int64_t last_best_index = -1;
@@ -338,17 +375,20 @@ private:
         return lk;
     }
 
+    void ensure_scene() {
+        if (scene_) return;
+        sspp_scene* s = nullptr;
+        // count_static = 1: checkCollision's ncon is the whole scene's (include/sspp.h:143-144,
+        // Q7), static-static contacts included
+        ck(sspp_scene_create(model_.get(), SSPP_MODE_QPOS, N, 1, &s), "scene");
+        scene_.reset(s);
+    }
+
     void ensure_planner() {
         if (planner_) return;
         using clk = std::chrono::steady_clock;
         const auto t0 = clk::now();
-        if (!scene_) {
-            sspp_scene* s = nullptr;
-            // count_static = 1: checkCollision's ncon is the whole scene's (include/sspp.h:143-144,
-            // Q7), static-static contacts included
-            ck(sspp_scene_create(model_.get(), SSPP_MODE_QPOS, N, 1, &s), "scene");
-            scene_.reset(s);
-        }
+        ensure_scene();
         const auto t1 = clk::now();
         sspp_planner* p = nullptr;
         ck(sspp_planner_create(scene_.get(), N, &p), "planner");
@@ -419,6 +459,10 @@ void bind(py::module& m, const std::string& planner_name, const std::string& spl
         .def("plan_many", &P::plan_many, py::arg("starts"), py::arg("ends"), py::arg("sigma"), py::arg("limits"),
              py::arg("sample_count") = 50, py::arg("check_points") = 50, py::arg("init_points") = 10,
              py::arg("seeds") = py::none())
+        .def("set_qpos", &P::set_qpos, py::arg("qpos"))
+        .def("set_body_pose", &P::set_body_pose, py::arg("name"), py::arg("pos"), py::arg("quat"))
+        .def("get_qpos", &P::get_qpos)
+        .def("_option", &P::option, py::arg("key"))
         .def_readwrite("seed", &P::seed)
         .def_readonly("last_best_cost", &P::last_best_cost)
         .def_readonly("last_best_index", &P::last_best_index)

@@ -229,6 +229,29 @@ public:
         return spline_through(pts);
     }
     int n_vias() const { return K_; }
+    // Re-posing the scene in place (sspp_scene_set_qpos / _set_body_pose; not the reference's
+    // API): the CES distribution, forwarded best and iteration count are kept, so
+    // plan(start, end, True) continues from them in the new world.
+    void set_qpos(py::array_t<double, py::array::forcecast> qpos) {
+        py::array_t<double> c = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(qpos);
+        ck(sspp_scene_set_qpos(scene_.get(), c.data(), (int)c.size()), "set_qpos");
+    }
+    void set_body_pose(const std::string& name, py::array_t<double, py::array::forcecast> pos,
+                       py::array_t<double, py::array::forcecast> quat) {
+        py::array_t<double> p = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(pos);
+        py::array_t<double> q = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(quat);
+        if (p.size() != 3 || q.size() != 4) throw py::value_error("set_body_pose: pos needs 3 values, quat 4");
+        const int body = sspp_model_body_id(model_.get(), name.c_str());
+        ck(body, "set_body_pose");
+        ck(sspp_scene_set_body_pose(scene_.get(), body, p.data(), q.data()), "set_body_pose");
+    }
+    py::array_t<double> get_qpos() const {
+        sspp_model_view v{};
+        ck(sspp_model_view_get(model_.get(), &v), "get_qpos");
+        py::array_t<double> out((ssize_t)v.nq);
+        ck(sspp_scene_get_qpos(scene_.get(), out.mutable_data(), v.nq), "get_qpos");
+        return out;
+    }
     sspp_ces_state last_state_{};
 
 private:
@@ -377,6 +400,9 @@ PYBIND11_MODULE(_tsp, m) {
                  return p.spline_from_vias(vs);
              }, py::arg("vias"))
         .def("reset", [](P&) {})
+        .def("set_qpos", &P::set_qpos, py::arg("qpos"))
+        .def("set_body_pose", &P::set_body_pose, py::arg("name"), py::arg("pos"), py::arg("quat"))
+        .def("get_qpos", &P::get_qpos)
         .def_property_readonly("last_n_success", [](const P& p) { return p.last_state_.n_success; })
         .def_property_readonly("last_best_slot", [](const P& p) { return p.last_state_.best_slot; })
         .def_property_readonly("last_best_cost", [](const P& p) { return p.last_state_.best_cost; });

@@ -173,6 +173,35 @@ class Scene:
         check(lib().sspp_scene_get_info(self._h, C.byref(i)), "scene info")
         return {k: getattr(i, k) for k, _ in SceneInfo._fields_}
 
+    # Re-posing in place (sspp_scene_set_qpos / _set_body_pose): host-synchronous; no launch that
+    # uses the scene may be in flight on the caller's streams.  Every job, planner, executor and
+    # CES planner bound to the scene then works in the new world, as fresh objects on a scene
+    # loaded with these values would; a captured graph must be captured again.
+    def set_qpos(self, qpos):
+        """Every free body's pose at once: qpos [nq] in the model's layout (pos, quat each)."""
+        q = _f64(qpos)
+        check(lib().sspp_scene_set_qpos(self._h, _dptr(q), int(q.size)), "scene set_qpos")
+
+    def set_body_pose(self, body, pos, quat):
+        """One body (id or name): a free body's 7 qpos, or a jointless body's pos / quat relative
+        to its parent; children follow."""
+        if isinstance(body, str):
+            body = self.model.body_id(body)
+        p, q = _f64(pos, 3), _f64(quat, 4)
+        check(lib().sspp_scene_set_body_pose(self._h, int(body), _dptr(p), _dptr(q)), "scene set_body_pose")
+
+    def qpos(self):
+        nq = int(self.model.arrays()["qpos0"].size)
+        out = np.zeros(nq)
+        check(lib().sspp_scene_get_qpos(self._h, _dptr(out), nq), "scene qpos")
+        return out
+
+    @property
+    def epoch(self):
+        v = C.c_int64()
+        check(lib().sspp_scene_epoch(self._h, C.byref(v)), "scene epoch")
+        return int(v.value)
+
     def __del__(self):
         if getattr(self, "_h", None) and _lib._lib is not None:
             _lib._lib.sspp_scene_free(self._h)
