@@ -21,7 +21,7 @@ PYINC    = $(shell $(PY) -c "import sysconfig;print(sysconfig.get_paths()['inclu
 PBINC    = $(shell $(PY) -c "import pybind11;print(pybind11.get_include())")
 
 HDRS = include/sspp_hip.h $(SRC)/sspp_logtab.h $(SRC)/model.h $(SRC)/sspp_own.h $(SRC)/sspp_device.h $(SRC)/sspp_filter.h $(SRC)/xml_lite.h $(SRC)/sspp_kern.h $(SRC)/sspp_scene_build.h \
-       $(SRC)/sspp_prof.h $(SRC)/sspp_knobs.h $(SRC)/sspp_lds.h $(SRC)/sspp_rng.h
+       $(SRC)/sspp_prof.h $(SRC)/sspp_knobs.h $(SRC)/sspp_lds.h $(SRC)/sspp_rng.h $(SRC)/sspp_report.h
 # kernel instantiations, one translation unit per (dof, degree) (+ d0: TaskSpacePlanner), compiled
 # in parallel (one unit per degree also keeps the register allocation of each kernel its own)
 INST = $(OBJDIR)/sspp_inst_d0.o $(foreach d,1 2 3 4 6 7 9,$(foreach p,2 3,$(OBJDIR)/sspp_inst_d$(d)_p$(p).o))
@@ -59,7 +59,8 @@ $(OBJDIR)/stamp.o: $(SRCS) sspp_amd/_stamp.py
 	@printf 'extern "C" const char* sspp_build_id() { return "%s"; }\n' `$(PY) sspp_amd/_stamp.py` > $(OBJDIR)/stamp.cpp
 	g++ $(HOSTFLAGS) -c $(OBJDIR)/stamp.cpp -o $@
 
-$(LIB): $(OBJDIR)/sspp_kernels.o $(INST) $(OBJDIR)/ces.o $(OBJDIR)/planner.o $(OBJDIR)/sspp_capi.o $(OBJDIR)/mjcf.o $(OBJDIR)/spline_host.o $(OBJDIR)/sspp_hostapi.o $(OBJDIR)/stamp.o
+# the contact report's kernels (sspp_scene_contacts, sspp_job_path_contacts): a unit of their own
+$(LIB): $(OBJDIR)/sspp_kernels.o $(INST) $(OBJDIR)/sspp_report.o $(OBJDIR)/ces.o $(OBJDIR)/planner.o $(OBJDIR)/sspp_capi.o $(OBJDIR)/mjcf.o $(OBJDIR)/spline_host.o $(OBJDIR)/sspp_hostapi.o $(OBJDIR)/stamp.o
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 

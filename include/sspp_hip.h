@@ -41,6 +41,10 @@
  *                               (repeated `iterations` times, no host round trip)
  *   sspp_ces_read            <- successes()/failures()/sampled_sets()/mean()/sigma() getters
  *                               tsp_planner.h:151-158, tsp.h:63-78
+ *   sspp_scene_contacts      <- reading mjData::contact[] after mj_forward, as
+ *   sspp_job_path_contacts      Collision::check_collision_point does            include/Collision.h:51-82
+ *   sspp_scene_pairs / _static_pairs, sspp_model_geom_name / _body_name
+ *                            <- mjContact::geom1 / geom2 and mj_id2name          (same lines)
  *
  * Device pointers: every `d_` argument is device memory (hipMalloc / torch.cuda); the job
  * run functions issue only asynchronous work on `stream` (hipStream_t passed as void*; NULL =
@@ -229,6 +233,64 @@ int sspp_scene_set_qpos(sspp_scene* s, const double* qpos, int nq);
 int sspp_scene_set_body_pose(sspp_scene* s, int body, const double pos[3], const double quat[4]);
 int sspp_scene_get_qpos(const sspp_scene* s, double* qpos_out, int nq);
 int sspp_scene_epoch(const sspp_scene* s, int64_t* epoch);
+
+/* ---- contact report: which geom pairs a pose or a path touches ----
+ * Stands for reading mjData::contact[] after mj_forward, as Collision::check_collision_point
+ * (include/Collision.h:51-82) does to name the two geoms of a deep contact.  Per pair of the
+ * scene's pair table and per pose, two counts (uint8_t):
+ *   contact  the pair's contacts with dist < margin: the count behind SamplingPathPlanner's
+ *            ncon > 0 (include/sspp.h:139-147) and behind sspp_scene_info::static_contacts.  A
+ *            true count for the primitive colliders (up to 4 for plane-box and plane-cylinder),
+ *            0 / 1 for box-box, cylinder-box and cylinder-cylinder pairs
+ *   deep     the contacts with dist < -1e-3: the multiplicity of Collision.h's cost terms
+ *            (include/Collision.h:84-103), up to 8 for a box-box manifold; deep > contact is
+ *            normal for box-box
+ * A pair the scoring's broadphase culls reports 0 / 0.  Outputs are dense: every entry is written,
+ * zeros included.
+ *   sspp_scene_pairs         the n_pairs moving pairs in report column order: grouped by moving
+ *                            geom in SSPP_MODE_QPOS, (geom1, geom2) order in SSPP_MODE_BODY
+ *   sspp_scene_static_pairs  the n_static_pairs env-env pairs, (geom1, geom2) order, with their
+ *                            counts at the scene's current poses (they sum to static_contacts;
+ *                            a scene update recomputes them)
+ *   Both: out (and contact / deep) may be NULL to read *n only; cap < n is SSPP_E_INVAL.
+ *   sspp_model_geom_name / _body_name   the names sspp_model_geom_id / _body_id look up: "" for an
+ *                            unnamed one, NULL out of range; valid while the model lives
+ *   sspp_scene_contacts      N poses -> [N][n_pairs] counts.  d_q: [N][dof] (SSPP_MODE_QPOS) or
+ *                            [N][4] = (x, y, z, yaw) (SSPP_MODE_BODY); d_deep may be NULL
+ *   sspp_job_path_contacts   B paths of a job -> [B][Wn][n_pairs] counts at the job's collision
+ *                            waypoints, bit for bit the poses its scoring kernels test.
+ *                            SamplingPathPlanner job: d_paths = control points [B][n][D]
+ *                            (sspp_job_score_ctrl's), Wn = check_points + 1, waypoint i at
+ *                            u = i / check_points (checkCollision's grid).  TaskSpacePlanner job:
+ *                            d_paths = via sets [B][K][4] (sspp_job_tsp_score_vias'), Wn =
+ *                            check_points, waypoint i - 1 at u = i / check_points, i = 1..check_points
+ *                            (eval_one_pass's grid, which skips u = 0).  Columns are the scene's
+ *                            full pair table whatever the job's scan order, culls or filters.
+ * The two device calls are asynchronous on `stream`, allocate nothing and do not synchronise;
+ * N (B) = 0 or n_pairs = 0 is SSPP_OK without a launch; a NULL d_q (d_paths) or d_contact with
+ * something to write is SSPP_E_INVAL; a job whose scene was freed is SSPP_E_SCENE. */
+typedef struct sspp_pair_info {
+    int32_t geom1, geom2;     /* model geom indices, geom1 < geom2 */
+    int32_t moving1, moving2; /* 1: the geom rides a moving body of this scene */
+    double margin;            /* max of the two geoms' margins */
+} sspp_pair_info;
+int sspp_scene_pairs(const sspp_scene* s, sspp_pair_info* out, int cap, int* n);
+int sspp_scene_static_pairs(const sspp_scene* s, sspp_pair_info* out, uint8_t* contact, uint8_t* deep,
+                            int cap, int* n);
+const char* sspp_model_geom_name(const sspp_model* m, int geom);
+const char* sspp_model_body_name(const sspp_model* m, int body);
+int sspp_scene_contacts(const sspp_scene* s, const double* d_q, int64_t N, uint8_t* d_contact /* [N][P] */,
+                        uint8_t* d_deep /* [N][P], nullable */, void* stream);
+int sspp_job_path_contacts(sspp_job* job, const double* d_paths, int64_t B, uint8_t* d_contact /* [B][Wn][P] */,
+                           uint8_t* d_deep /* nullable */, void* stream);
+/* The same on host buffers, host-synchronous (the drop-in planners' contact_report): q [N][dof] or
+ * [N][4]; B splines (knots, degree, ctrl [B][n][dof]) on checkCollision's grid of num_samples + 1
+ * waypoints, through a job made for the call.  deep may be NULL.  They run on the drop-in
+ * planners' shared stream and wait for that stream only. */
+int sspp_scene_contacts_host(const sspp_scene* s, const double* q, int64_t N, uint8_t* contact, uint8_t* deep);
+int sspp_path_contacts_host(const sspp_scene* s, const double* knots, int degree, const double* ctrl /* [B][n][dof] */,
+                            int64_t B, int n, int num_samples, uint8_t* contact /* [B][num_samples + 1][P] */,
+                            uint8_t* deep);
 
 /* ---- splines (host) ---- */
 int sspp_interpolate(const double* pts /* [n][D] */, int n, int D, int degree,

@@ -50,6 +50,11 @@ class SceneInfo(C.Structure):
                 ("n_movers", C.c_int), ("static_cost", C.c_double)]
 
 
+class PairInfo(C.Structure):
+    _fields_ = [("geom1", C.c_int32), ("geom2", C.c_int32), ("moving1", C.c_int32), ("moving2", C.c_int32),
+                ("margin", C.c_double)]
+
+
 class SsppArgs(C.Structure):
     _fields_ = [("knots", C.POINTER(C.c_double)), ("degree", C.c_int),
                 ("init_ctrl", C.POINTER(C.c_double)), ("n_ctrl", C.c_int), ("dof", C.c_int),
@@ -114,6 +119,15 @@ SIGNATURES = {
     "sspp_scene_set_body_pose": (C.c_int, [_vp, _i, _d, _d]),
     "sspp_scene_get_qpos": (C.c_int, [_vp, _d, _i]),
     "sspp_scene_epoch": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "sspp_scene_pairs": (C.c_int, [_vp, C.POINTER(PairInfo), _i, C.POINTER(C.c_int)]),
+    "sspp_scene_static_pairs": (C.c_int, [_vp, C.POINTER(PairInfo), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _i,
+                                          C.POINTER(C.c_int)]),
+    "sspp_model_geom_name": (C.c_char_p, [_vp, _i]),
+    "sspp_model_body_name": (C.c_char_p, [_vp, _i]),
+    "sspp_scene_contacts": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "sspp_job_path_contacts": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "sspp_scene_contacts_host": (C.c_int, [_vp, _d, _i64, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "sspp_path_contacts_host": (C.c_int, [_vp, _d, _i, _d, _i64, _i, _i, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "sspp_interpolate": (C.c_int, [_d, _i, _i, _i, _d, _d, _d]),
     "sspp_spline_eval": (C.c_int, [_d, _i, _i, _d, _i, C.c_double, _d]),
     "sspp_job_create_sspp": (C.c_int, [_vp, C.POINTER(SsppArgs), _i64, C.POINTER(_vp)]),

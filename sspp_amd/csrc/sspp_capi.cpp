@@ -73,6 +73,17 @@ int sspp_model_geom_id(const sspp_model* m, const char* name) {
     return sspp::set_error(SSPP_E_SCENE, std::string("Geom with name '") + name + "' not found.");
 }
 
+// the inverse look-ups (mj_id2name): "" for an unnamed one, NULL out of range
+const char* sspp_model_geom_name(const sspp_model* m, int geom) {
+    if (!m || geom < 0 || geom >= m->ngeom()) return nullptr;
+    return m->geom_names[geom].c_str();
+}
+
+const char* sspp_model_body_name(const sspp_model* m, int body) {
+    if (!m || body < 0 || body >= m->nbody()) return nullptr;
+    return m->body_names[body].c_str();
+}
+
 // Utility::get_body_point (include/utility.h:228-259): (x, y, z, yaw) of a free body at
 // qpos0; yaw = ZYX-Euler yaw of the joint quaternion (atan2 form; equal to Eigen's
 // eulerAngles(2,1,0)[0] for the shipped scenes' pure-yaw orientations).

@@ -101,7 +101,7 @@ typedef const SSPP_CONST DGeom* cgeom_t;
 typedef const SSPP_CONST DPair* cpair_t;
 typedef const SSPP_CONST DMover* cmover_t;
 
-__device__ __forceinline__ DGeom load_geom(cgeom_t p) {
+SSPP_HD DGeom load_geom(cgeom_t p) {
     DGeom g;
 #pragma unroll
     for (int k = 0; k < 3; ++k) g.pos[k] = p->pos[k];
@@ -117,7 +117,7 @@ __device__ __forceinline__ DGeom load_geom(cgeom_t p) {
     g.relrot = p->relrot;
     return g;
 }
-__device__ __forceinline__ DPair load_pair(cpair_t p) {
+SSPP_HD DPair load_pair(cpair_t p) {
     DPair r;
     r.gm = p->gm;
     r.go = p->go;
@@ -287,9 +287,10 @@ __device__ __forceinline__ double wave_sum(double v) {
 // ---------------------------------------------------------------- one waypoint vs the scene
 // Mover root poses (position + rotation) for MODE 0 (q -> qpos[0:D] window, free joints at
 // qpos[7m:7m+7]) or MODE 1 ((x, y, z, yaw) -> the bound free body, utility.h:149-206).
+// (This and the geom pose helpers below are __host__ __device__: the contact report's per-pose
+// routine, sspp_report.h, also runs on the CPU.)
 template <int D, int NM, int MODE>
-__device__ __forceinline__ void mover_poses(const double* q, cmover_t movers,
-                                            double (&mp)[NM][3], double (&mR)[NM][9]) {
+SSPP_HD void mover_poses(const double* q, cmover_t movers, double (&mp)[NM][3], double (&mR)[NM][9]) {
 #pragma unroll
     for (int m = 0; m < NM; ++m) {
         double qp[7];
@@ -342,12 +343,12 @@ __device__ __forceinline__ void geom_pose(const double* P, const double* R, cons
     }
 }
 
-__device__ __forceinline__ void geom_pos(const double* P, const double* R, const DGeom& G, double* gp) {
+SSPP_HD void geom_pos(const double* P, const double* R, const DGeom& G, double* gp) {
     double t[3];
     matvec3(R, G.pos, t);
     gp[0] = P[0] + t[0]; gp[1] = P[1] + t[1]; gp[2] = P[2] + t[2];
 }
-__device__ __forceinline__ void geom_rot(const double* R, const DGeom& G, double* gm) {
+SSPP_HD void geom_rot(const double* R, const DGeom& G, double* gm) {
     if (G.relrot) {
         matmul3(R, G.mat, gm);
     } else {
@@ -359,14 +360,14 @@ __device__ __forceinline__ void geom_rot(const double* R, const DGeom& G, double
 // Geom pose from a mover rotation about z (R[2] = R[5] = R[6] = R[7] = 0, MODE 1): the
 // generic dot products with those zero terms dropped (each dropped term adds an exact zero).
 template <bool ZR>
-__device__ __forceinline__ void geom_pos_t(const double* P, const double* R, const DGeom& G, double* gp) {
+SSPP_HD void geom_pos_t(const double* P, const double* R, const DGeom& G, double* gp) {
     if (!ZR) { geom_pos(P, R, G, gp); return; }
     gp[0] = P[0] + fma(R[1], G.pos[1], R[0] * G.pos[0]);
     gp[1] = P[1] + fma(R[4], G.pos[1], R[3] * G.pos[0]);
     gp[2] = P[2] + R[8] * G.pos[2];
 }
 template <bool ZR>
-__device__ __forceinline__ void geom_rot_t(const double* R, const DGeom& G, double* gm) {
+SSPP_HD void geom_rot_t(const double* R, const DGeom& G, double* gm) {
     if (!ZR || !G.relrot) { geom_rot(R, G, gm); return; }
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
@@ -2708,6 +2709,16 @@ inline size_t tsp_base_lds(int cpb, int n, int rep) {
 using namespace sspk;
 using namespace sspo;
 
+namespace sspb {
+// an env-env pair with its counts at the scene's poses (sspp_scene_static_pairs): `contact` what
+// collide<false> returns, `deep` collide<true>'s *nd; 0 / 0 for a pair the bounding spheres cull
+struct StaticPair {
+    int g1, g2;  // model geom indices, g1 < g2
+    double margin;
+    uint8_t contact, deep;
+};
+}  // namespace sspb
+
 struct sspp_scene {
     int mode, arg, dof;
     int count_static;
@@ -2716,6 +2727,7 @@ struct sspp_scene {
     std::vector<DMover> movers;
     int n_moving_geoms = 0, n_static_geoms = 0, n_static_pairs = 0, static_contacts = 0;
     double static_cost = 0.0;
+    std::vector<sspb::StaticPair> statics;  // the env-env pairs with their counts (sspp_scene_static_pairs)
     Dev<DGeom> d_geoms;
     Dev<DPair> d_pairs;  // (null without pairs, as d_visit without a visit order)
     Dev<DMover> d_movers;

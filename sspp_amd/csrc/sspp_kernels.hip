@@ -83,6 +83,7 @@ static int scene_adopt(sspp_scene* s, sspb::SceneTables&& t, bool create) {
     s->n_moving_geoms = t.n_moving_geoms; s->n_static_geoms = t.n_static_geoms;
     s->n_static_pairs = t.n_static_pairs; s->static_contacts = t.static_contacts;
     s->static_cost = t.static_cost;
+    s->statics = std::move(t.statics);
     int rc;
     if ((rc = s->d_geoms.upload(s->geoms.data(), s->geoms.size())) ||
         (rc = s->d_pairs.upload(s->pairs.data(), s->pairs.size())) ||

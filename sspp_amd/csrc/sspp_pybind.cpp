@@ -265,6 +265,45 @@ public:
         return feas == 0;
     }
 
+    // Which geom pairs checkCollision(spline, num_samples) counts (not the reference's API, whose
+    // users read mjData's contact[] themselves, as Collision::check_collision_point does,
+    // include/Collision.h:51-82): a list of (waypoint, u, geom1 name, geom2 name, contacts) — the
+    // env-env pairs in contact first (waypoint -1, u nan: they hold at every waypoint), then the
+    // moving pairs in (waypoint, pair) order.  bool(report) == checkCollision(spline, num_samples).
+    py::list contact_report(const Spline<N>& s, int num_samples) {
+        if (num_samples < 1) throw py::value_error("num_samples must be >= 1");
+        if (s.ctrl.empty()) throw py::value_error("contact_report on an empty spline");
+        auto lk = lock();
+        ensure_scene();
+        int np = 0, ns = 0;
+        ck(sspp_scene_pairs(scene_.get(), nullptr, 0, &np), "contact_report");
+        ck(sspp_scene_static_pairs(scene_.get(), nullptr, nullptr, nullptr, 0, &ns), "contact_report");
+        std::vector<sspp_pair_info> pi((size_t)np), si((size_t)ns);
+        std::vector<uint8_t> sc((size_t)ns), sd((size_t)ns), c((size_t)(num_samples + 1) * np);
+        ck(sspp_scene_pairs(scene_.get(), pi.data(), np, &np), "contact_report");
+        ck(sspp_scene_static_pairs(scene_.get(), si.data(), sc.data(), sd.data(), ns, &ns), "contact_report");
+        if (np > 0) {
+            std::vector<double> ctrl = s.ctrl_nd();
+            int rc;
+            {
+                py::gil_scoped_release nogil;
+                rc = sspp_path_contacts_host(scene_.get(), s.knots.data(), 3, ctrl.data(), 1, s.n(), num_samples,
+                                             c.data(), nullptr);
+            }
+            ck(rc, "contact_report");
+        }
+        auto name = [&](int g) { return std::string(sspp_model_geom_name(model_.get(), g)); };
+        py::list out;
+        for (int k = 0; k < ns; ++k)
+            if (sc[k]) out.append(py::make_tuple(-1, std::nan(""), name(si[k].geom1), name(si[k].geom2), (int)sc[k]));
+        for (int i = 0; i <= num_samples; ++i)
+            for (int k = 0; k < np; ++k)
+                if (c[(size_t)i * np + k])
+                    out.append(py::make_tuple(i, (double)i / num_samples, name(pi[k].geom1), name(pi[k].geom2),
+                                              (int)c[(size_t)i * np + k]));
+        return out;
+    }
+
     double computeArcLength(const Spline<N>& s, int check_points) {
         if (check_points < 2) throw py::value_error("check_points must be >= 2");
         if (s.ctrl.empty()) throw py::value_error("computeArcLength on an empty spline");
@@ -450,6 +489,7 @@ void bind(py::module& m, const std::string& planner_name, const std::string& spl
              py::arg("limits"), py::arg("generator"))
         .def("checkCollision", &P::checkCollision, py::arg("spline"), py::arg("num_samples"),
              py::arg("data") = py::none())
+        .def("contact_report", &P::contact_report, py::arg("spline"), py::arg("num_samples"))
         .def("computeArcLength", &P::computeArcLength, py::arg("spline"), py::arg("check_points"))
         .def("findBestPath", &P::findBestPath, py::arg("successful_paths"), py::arg("best_spline"),
              py::arg("check_points") = 10)

@@ -57,6 +57,7 @@ struct SceneTables {
     std::vector<DMover> movers;
     int n_moving_geoms = 0, n_static_geoms = 0, n_static_pairs = 0, static_contacts = 0;
     double static_cost = 0.0;
+    std::vector<StaticPair> statics;  // the n_static_pairs env-env pairs, (g1, g2) order
 };
 
 // The tables of model m (poses: its qpos0 / body_pos / body_quat) for the moving bodies
@@ -147,6 +148,7 @@ inline int scene_build(const sspp_model& mdl, int mode, const std::vector<int>& 
     for (auto& pr : all) {
         if (!pr.stat) continue;
         s->n_static_pairs++;
+        s->statics.push_back({pr.g1, pr.g2, pr.margin, 0, 0});
         const DGeom& A = s->geoms[table_index[pr.g1]];
         const DGeom& B = s->geoms[table_index[pr.g2]];
         double dc[3] = {B.pos[0] - A.pos[0], B.pos[1] - A.pos[1], B.pos[2] - A.pos[2]};
@@ -161,6 +163,8 @@ inline int scene_build(const sspp_model& mdl, int mode, const std::vector<int>& 
         int nc = collide<false>(F.type, F.pos, F.mat, F.size, S.type, S.pos, S.mat, S.size, pr.margin, &nd);
         collide<true>(F.type, F.pos, F.mat, F.size, S.type, S.pos, S.mat, S.size, pr.margin, &nd);
         s->static_contacts += nc;
+        s->statics.back().contact = (uint8_t)nc;
+        s->statics.back().deep = (uint8_t)nd;
         if (nd > 0) {
             double term = -1.0 / (sqrt(dot3(dc, dc)) + 1e-4);
             for (int i = 0; i < nd; ++i) s->static_cost = s->static_cost + term;

@@ -252,6 +252,38 @@ public:
         ck(sspp_scene_get_qpos(scene_.get(), out.mutable_data(), v.nq), "get_qpos");
         return out;
     }
+    // The pairs with a deep contact (dist < -1e-3) at (x, y, z, yaw), env-env pairs included: a list
+    // of (geom1 name, geom2 name, deep count) — what Collision::check_collision_point
+    // (include/Collision.h:51-82) walks mjData's contact[] for, without its printing.
+    py::list contact_report(py::array_t<double, py::array::forcecast> point) const {
+        py::array_t<double> q = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(point);
+        if (q.size() != 4) throw py::value_error("contact_report: a point is (x, y, z, yaw)");
+        int np = 0, ns = 0;
+        ck(sspp_scene_pairs(scene_.get(), nullptr, 0, &np), "contact_report");
+        ck(sspp_scene_static_pairs(scene_.get(), nullptr, nullptr, nullptr, 0, &ns), "contact_report");
+        std::vector<sspp_pair_info> pi((size_t)np), si((size_t)ns);
+        std::vector<uint8_t> sc((size_t)ns), sd((size_t)ns), c((size_t)np), d((size_t)np);
+        ck(sspp_scene_pairs(scene_.get(), pi.data(), np, &np), "contact_report");
+        ck(sspp_scene_static_pairs(scene_.get(), si.data(), sc.data(), sd.data(), ns, &ns), "contact_report");
+        if (np > 0) {
+            int rc;
+            {
+                py::gil_scoped_release nogil;
+                rc = sspp_scene_contacts_host(scene_.get(), q.data(), 1, c.data(), d.data());
+            }
+            ck(rc, "contact_report");
+        }
+        auto name = [&](int g) { return std::string(sspp_model_geom_name(model_.get(), g)); };
+        py::list out;
+        for (int k = 0; k < ns; ++k)
+            if (sd[k]) out.append(py::make_tuple(name(si[k].geom1), name(si[k].geom2), (int)sd[k]));
+        for (int k = 0; k < np; ++k)
+            if (d[k]) out.append(py::make_tuple(name(pi[k].geom1), name(pi[k].geom2), (int)d[k]));
+        return out;
+    }
+    bool check_collision_point(py::array_t<double, py::array::forcecast> point) const {
+        return py::len(contact_report(point)) > 0;
+    }
     sspp_ces_state last_state_{};
 
 private:
@@ -403,6 +435,8 @@ PYBIND11_MODULE(_tsp, m) {
         .def("set_qpos", &P::set_qpos, py::arg("qpos"))
         .def("set_body_pose", &P::set_body_pose, py::arg("name"), py::arg("pos"), py::arg("quat"))
         .def("get_qpos", &P::get_qpos)
+        .def("contact_report", &P::contact_report, py::arg("point"))
+        .def("check_collision_point", &P::check_collision_point, py::arg("point"))
         .def_property_readonly("last_n_success", [](const P& p) { return p.last_state_.n_success; })
         .def_property_readonly("last_best_slot", [](const P& p) { return p.last_state_.best_slot; })
         .def_property_readonly("last_best_cost", [](const P& p) { return p.last_state_.best_cost; });

@@ -11,8 +11,8 @@ import math
 import numpy as np
 
 from . import _lib
-from ._lib import (Best, CesBuffers, CesConfig, CesInfo, CesState, ModelView, SceneInfo,
-                   SsppArgs, TspArgs, check, lib)
+from ._lib import (Best, CesBuffers, CesConfig, CesInfo, CesState, ModelView, PairInfo, SceneInfo,
+                   SsppArgs, SsppError, TspArgs, check, lib)
 
 DEFAULT_SEED = 0x5EED
 SAMPLER_FP64, SAMPLER_FP32 = 0, 1  # sspp_sspp_args::sampler
@@ -45,6 +45,16 @@ def _stream(stream):
     if isinstance(stream, int):
         return C.c_void_p(stream)
     return C.c_void_p(stream.cuda_stream)
+
+
+def _sync(stream):
+    torch = _torch()
+    if stream is None:
+        torch.cuda.current_stream().synchronize()
+    elif isinstance(stream, int):
+        torch.cuda.synchronize()
+    else:
+        stream.synchronize()
 
 
 def best_tensor(device="cuda"):
@@ -142,6 +152,19 @@ class Model:
     def geom_id(self, name):
         return check(lib().sspp_model_geom_id(self._h, name.encode()), "geom lookup")
 
+    def geom_name(self, geom):
+        """The geom's name ("" when unnamed): the inverse of geom_id."""
+        r = lib().sspp_model_geom_name(self._h, int(geom))
+        if r is None:
+            raise SsppError("geom id %d out of range" % int(geom))
+        return r.decode()
+
+    def body_name(self, body):
+        r = lib().sspp_model_body_name(self._h, int(body))
+        if r is None:
+            raise SsppError("body id %d out of range" % int(body))
+        return r.decode()
+
     def body_point(self, name):
         out = np.zeros(4)
         check(lib().sspp_model_body_point(self._h, name.encode(), _dptr(out)), "body point")
@@ -202,6 +225,56 @@ class Scene:
         check(lib().sspp_scene_epoch(self._h, C.byref(v)), "scene epoch")
         return int(v.value)
 
+    # Contact report (sspp_scene_pairs / _static_pairs / _contacts): which geom pairs a pose touches,
+    # what the reference reads from mjData.contact[] (Collision::check_collision_point).
+    def _pair_dicts(self, infos, contact=None, deep=None):
+        gt = self.model.arrays()["geom_type"]
+        out = []
+        for k, p in enumerate(infos):
+            d = dict(geom1=int(p.geom1), geom2=int(p.geom2), name1=self.model.geom_name(p.geom1),
+                     name2=self.model.geom_name(p.geom2), type1=int(gt[p.geom1]), type2=int(gt[p.geom2]),
+                     moving1=bool(p.moving1), moving2=bool(p.moving2), margin=float(p.margin))
+            if contact is not None:
+                d["contact"], d["deep"] = int(contact[k]), int(deep[k])
+            out.append(d)
+        return out
+
+    def pairs(self):
+        """The moving pairs in report column order: a list of dicts (geom ids, names, types, margin)."""
+        n = C.c_int()
+        check(lib().sspp_scene_pairs(self._h, None, 0, C.byref(n)), "scene pairs")
+        infos = (PairInfo * max(n.value, 1))()
+        check(lib().sspp_scene_pairs(self._h, infos, n.value, C.byref(n)), "scene pairs")
+        return self._pair_dicts(infos[:n.value])
+
+    def static_pairs(self):
+        """The env-env pairs with their `contact` / `deep` counts at the scene's current poses."""
+        n = C.c_int()
+        check(lib().sspp_scene_static_pairs(self._h, None, None, None, 0, C.byref(n)), "scene static pairs")
+        infos = (PairInfo * max(n.value, 1))()
+        c, d = (C.c_uint8 * max(n.value, 1))(), (C.c_uint8 * max(n.value, 1))()
+        check(lib().sspp_scene_static_pairs(self._h, infos, c, d, n.value, C.byref(n)), "scene static pairs")
+        return self._pair_dicts(infos[:n.value], c, d)
+
+    def contacts(self, q, deep=True, stream=None):
+        """Per-pair contact counts of N poses: q [N, dof] (MODE_QPOS) or [N, 4] = (x, y, z, yaw)
+        (MODE_BODY), a CUDA tensor or an array.  Returns (contact, deep): uint8 tensors [N, P] in
+        pairs() column order (deep is None with deep=False).  Synchronises on its stream."""
+        torch = _torch()
+        D = int(self.arg) if self.mode == _lib.MODE_QPOS else 4
+        if not (hasattr(q, "is_cuda") and q.is_cuda):
+            q = torch.as_tensor(np.array(q, dtype=np.float64), device="cuda")
+        q = q.to(torch.float64).contiguous()
+        if q.ndim != 2 or q.shape[1] != D:
+            raise SsppError("contacts failed (-1): poses must be [N, %d], got %s" % (D, tuple(q.shape)))
+        N, P = int(q.shape[0]), self.info()["n_pairs"]
+        c = torch.empty((N, P), dtype=torch.uint8, device=q.device)
+        d = torch.empty((N, P), dtype=torch.uint8, device=q.device) if deep else None
+        st = _stream(stream)
+        check(lib().sspp_scene_contacts(self._h, _ptr(q), N, _ptr(c), _ptr(d), st), "scene contacts")
+        _sync(stream)
+        return c, d
+
     def __del__(self):
         if getattr(self, "_h", None) and _lib._lib is not None:
             _lib._lib.sspp_scene_free(self._h)
@@ -247,6 +320,24 @@ class _Job:
         v = C.c_int64()
         check(lib().sspp_job_get_option(self._h, int(key), C.byref(v)), "job get_option")
         return int(v.value)
+
+    def _path_contacts(self, paths, shape, Wn, deep, stream):
+        torch = _torch()
+        if not (hasattr(paths, "is_cuda") and paths.is_cuda):
+            paths = torch.as_tensor(np.array(paths, dtype=np.float64), device="cuda")
+        paths = paths.to(torch.float64).contiguous()
+        if paths.ndim != 3 or tuple(paths.shape[1:]) != shape:
+            raise SsppError("path_contacts failed (-1): paths must be [B, %d, %d], got %s"
+                            % (shape[0], shape[1], tuple(paths.shape)))
+        if self.scene is None:
+            raise SsppError("path_contacts failed (-3): the job has no scene")
+        B, P = int(paths.shape[0]), self.scene.info()["n_pairs"]
+        c = torch.empty((B, Wn, P), dtype=torch.uint8, device=paths.device)
+        d = torch.empty((B, Wn, P), dtype=torch.uint8, device=paths.device) if deep else None
+        check(lib().sspp_job_path_contacts(self._h, _ptr(paths), B, _ptr(c), _ptr(d), _stream(stream)),
+              "path_contacts")
+        _sync(stream)
+        return c, d
 
     def __del__(self):
         if getattr(self, "_h", None) and _lib._lib is not None:
@@ -345,6 +436,11 @@ class SsppJob(_Job):
         check(lib().sspp_job_score_ctrl(self._h, _ptr(ctrl), int(first_id), int(B), _ptr(arc),
                                         _ptr(feasible), _ptr(best), _stream(stream)), "score_ctrl")
 
+    def path_contacts(self, ctrl, deep=True, stream=None):
+        """Per-pair contact counts at every collision waypoint of B splines: ctrl [B, n, D] ->
+        (contact, deep) uint8 [B, W + 1, P], waypoint i at u = i / W (sspp_job_path_contacts)."""
+        return self._path_contacts(ctrl, (self.n, self.D), self.W + 1, deep, stream)
+
     def set_shape(self, nt=0, g1=0):
         """Force the k_sspp_c2f launch shape (threads per workgroup 64 / 256, phase-1 lanes per
         candidate); 0, 0 = chosen per launch.  Every shape gives the same results."""
@@ -408,6 +504,11 @@ class TspJob(_Job):
         check(lib().sspp_job_tsp_score_vias(self._h, _ptr(vias), int(first_id), int(B), _ptr(L),
                                             _ptr(Cnf), _ptr(Cwf), _ptr(status), _ptr(cost),
                                             _ptr(best), _stream(stream)), "tsp score_vias")
+
+    def path_contacts(self, vias, deep=True, stream=None):
+        """Per-pair contact counts at every check point of B via sets: vias [B, K, 4] -> (contact,
+        deep) uint8 [B, cp, P], row i - 1 at u = i / cp, i = 1..cp (sspp_job_path_contacts)."""
+        return self._path_contacts(vias, (self.K, 4), self.cp, deep, stream)
 
 
 class SsppSteps:
