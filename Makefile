@@ -59,8 +59,10 @@ $(OBJDIR)/stamp.o: $(SRCS) sspp_amd/_stamp.py
 	@printf 'extern "C" const char* sspp_build_id() { return "%s"; }\n' `$(PY) sspp_amd/_stamp.py` > $(OBJDIR)/stamp.cpp
 	g++ $(HOSTFLAGS) -c $(OBJDIR)/stamp.cpp -o $@
 
-# the contact report's kernels (sspp_scene_contacts, sspp_job_path_contacts): a unit of their own
-$(LIB): $(OBJDIR)/sspp_kernels.o $(INST) $(OBJDIR)/sspp_report.o $(OBJDIR)/ces.o $(OBJDIR)/planner.o $(OBJDIR)/sspp_capi.o $(OBJDIR)/mjcf.o $(OBJDIR)/spline_host.o $(OBJDIR)/sspp_hostapi.o $(OBJDIR)/stamp.o
+# the contact report's kernels (sspp_scene_contacts, sspp_job_path_contacts) and the articulated
+# movers' (sspp_chain_*): units of their own; sspp_chain.h is read by sspp_chain.hip alone
+$(OBJDIR)/sspp_chain.o: $(SRC)/sspp_chain.h
+$(LIB): $(OBJDIR)/sspp_kernels.o $(INST) $(OBJDIR)/sspp_report.o $(OBJDIR)/sspp_chain.o $(OBJDIR)/ces.o $(OBJDIR)/planner.o $(OBJDIR)/sspp_capi.o $(OBJDIR)/mjcf.o $(OBJDIR)/spline_host.o $(OBJDIR)/sspp_hostapi.o $(OBJDIR)/stamp.o
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 

@@ -45,6 +45,11 @@
  *   sspp_job_path_contacts      Collision::check_collision_point does            include/Collision.h:51-82
  *   sspp_scene_pairs / _static_pairs, sspp_model_geom_name / _body_name
  *                            <- mjContact::geom1 / geom2 and mj_id2name          (same lines)
+ *   sspp_model_load_mjcf_joints <- mj_loadXML on a model with hinge / slide joints (the reference's
+ *                               users plan for an arm: scripts/main.py:162-199)
+ *   sspp_chain_create / _fk / _contacts <- mj_forward on such a model (mj_kinematics + collision)
+ *   sspp_chain_score_ctrl / _sample_score <- checkCollision + computeArcLength + findBestPath
+ *                               (include/sspp.h:132-192) / plan's candidate loop (203-219) for it
  *
  * Device pointers: every `d_` argument is device memory (hipMalloc / torch.cuda); the job
  * run functions issue only asynchronous work on `stream` (hipStream_t passed as void*; NULL =
@@ -291,6 +296,101 @@ int sspp_scene_contacts_host(const sspp_scene* s, const double* q, int64_t N, ui
 int sspp_path_contacts_host(const sspp_scene* s, const double* knots, int degree, const double* ctrl /* [B][n][dof] */,
                             int64_t B, int n, int num_samples, uint8_t* contact /* [B][num_samples + 1][P] */,
                             uint8_t* deep);
+
+/* ---- articulated movers: hinge and slide joints (DESIGN.md §5 "Articulated movers") ----
+ * sspp_model_load_mjcf_joints is sspp_model_load_mjcf that also accepts <joint type="hinge|slide">:
+ * several per body, in document order; `axis` (default 0 0 1, normalised; zero: SSPP_E_SCENE), `pos`
+ * (default 0 0 0), `ref` -> qpos0 (a hinge's in degrees unless <compiler angle="radian">, a slide's
+ * in metres); <default><joint/> classes and childclass as for geoms; every other joint attribute is
+ * ignored.  Ball joints stay SSPP_E_UNSUPPORTED; a free joint beside other joints on one body is
+ * SSPP_E_SCENE.  qpos addresses follow body pre-order: 7 per free joint, 1 per hinge / slide.  In
+ * sspp_model_view a body with hinge / slide joints reports its first joint (type 2 slide, 3 hinge).
+ * Every consumer of a model but sspp_chain_create refuses one that has a hinge or a slide joint
+ * (sspp_scene_create: SSPP_E_UNSUPPORTED, naming the joint).
+ *
+ * A chain is such a model bound to SamplingPathPlanner's pose rule q[0:dof] -> qpos[0:dof] (the rest
+ * stay at qpos0; dof > nq is SSPP_E_INVAL).  A body is driven when it or an ancestor has a joint
+ * whose qpos address lies below dof; joints at or past dof are frozen at qpos0; the other bodies are
+ * static.  Kinematics: mj_kinematics restated (bodies in index order; per joint, in order, a slide
+ * moves the frame along its axis, a hinge turns it about its anchor).  Pairs: sspp_scene_create's
+ * filter (a body with a joint is its own weld; same-weld and parent-child welds skipped; <exclude>,
+ * contype / conaffinity; margin = the larger one; a needed capsule-cylinder pair is refused by
+ * name), self-collision pairs between driven bodies included; static-static pairs are evaluated
+ * once at creation (count_static: a contact among them makes every candidate infeasible).  A pose
+ * is in contact iff some pair passes the bounding-sphere test and its collider reports a contact.
+ * Limits (beyond them SSPP_E_UNSUPPORTED, the message says which): SSPP_CHAIN_MAX_BODIES driven
+ * bodies, dof <= SSPP_CHAIN_MAX_DOF, SSPP_CHAIN_MAX_PAIRS pairs.
+ *   sspp_chain_fk           N poses -> world position and rotation of every geom of the model
+ *                           (static ones included): the planner user's get_body_point
+ *   sspp_chain_contacts     N poses -> one byte each: 1 in contact
+ *   sspp_chain_score_ctrl   <- checkCollision (u = i / W, i = 0..W) + computeArcLength +
+ *                           findBestPath on B caller splines, sspp_job_score_ctrl's output contract:
+ *                           arc +inf for an infeasible candidate, best = lowest arc, lowest id on
+ *                           ties, count filled.  Arc lengths are a scene-less job's, bit for bit
+ *   sspp_chain_sample_score the same on sampleWithNoise's candidates (sspp_sample_ctrl_host's for
+ *                           the seed and ids); d_ctrl_out nullable
+ * The device calls are asynchronous on `stream`; N = 0 or B = 0 is SSPP_OK without a launch.  The
+ * scoring calls keep a scene-less job per spline shape (knots, n, W): the first call of a shape or
+ * of a larger B allocates, later ones do not.  Out of scope for a chain: TaskSpacePlanner / CES,
+ * plan_many, re-posing, the per-pair contact report, joint limits. */
+#define SSPP_JNT_FREE 0
+#define SSPP_JNT_SLIDE 2
+#define SSPP_JNT_HINGE 3
+#define SSPP_CHAIN_MAX_BODIES 16
+#define SSPP_CHAIN_MAX_DOF 16
+#define SSPP_CHAIN_MAX_PAIRS 512
+typedef struct sspp_joint_view {
+    int njnt;
+    const int32_t* jnt_type;     /* SSPP_JNT_* */
+    const int32_t* jnt_body;
+    const int32_t* jnt_qpos_adr;
+    const double* jnt_axis;      /* [njnt][3] unit, body frame */
+    const double* jnt_pos;       /* [njnt][3] body frame */
+    int nq;
+    const double* qpos0;         /* a hinge's / slide's reference value at its address */
+} sspp_joint_view;
+int sspp_model_load_mjcf_joints(const char* xml_path, sspp_model** out);
+int sspp_model_joints_get(const sspp_model* m, sspp_joint_view* out);
+const char* sspp_model_joint_name(const sspp_model* m, int joint);
+
+typedef struct sspp_chain sspp_chain;
+typedef struct sspp_chain_info {
+    int dof;
+    int n_driven_bodies;
+    int n_geoms;            /* every geom of the model (sspp_chain_fk's rows) */
+    int n_moving_geoms;     /* geoms of driven bodies */
+    int n_static_geoms;
+    int n_pairs;            /* pairs evaluated per pose */
+    int n_static_pairs;     /* static-static pairs (evaluated once at creation) */
+    int static_contacts;    /* contacts among them */
+} sspp_chain_info;
+int sspp_chain_create(const sspp_model* m, int dof, int count_static_contacts, sspp_chain** out);
+int sspp_chain_get_info(const sspp_chain* c, sspp_chain_info* out);
+void sspp_chain_free(sspp_chain* c);
+/* the pair table in evaluation order (out may be NULL to read *n only; cap < n is SSPP_E_INVAL) */
+int sspp_chain_pairs(const sspp_chain* c, sspp_pair_info* out, int cap, int* n);
+int sspp_chain_fk(const sspp_chain* c, const double* d_q /* [N][dof] */, int64_t N,
+                  double* d_gpos /* [N][n_geoms][3] */, double* d_gmat /* [N][n_geoms][9] */, void* stream);
+int sspp_chain_contacts(const sspp_chain* c, const double* d_q /* [N][dof] */, int64_t N,
+                        uint8_t* d_hit /* [N] */, void* stream);
+int sspp_chain_score_ctrl(sspp_chain* c, const double* knots /* host [n + degree + 1] */, int degree,
+                          const double* d_ctrl /* [B][n][dof] */, int64_t first_id, int64_t B, int n, int W,
+                          double* d_arc, uint8_t* d_feasible, sspp_best* d_best, void* stream);
+int sspp_chain_sample_score(sspp_chain* c, const double* knots, int degree, const double* init_ctrl /* host [n][dof] */,
+                            int n, int W, double sigma, const double* limits /* host [dof] */, uint64_t seed,
+                            int64_t first_id, int64_t B, double* d_arc, uint8_t* d_feasible,
+                            double* d_ctrl_out /* nullable [B][n][dof] */, sspp_best* d_best, void* stream);
+/* The same on host buffers, host-synchronous (the drop-in planner of an articulated model): poses
+ * q [N][dof]; B splines sharing one knot vector (with_collision = 0: arc length only); and
+ * SamplingPathPlanner::plan in one call, as sspp_plan_sspp. */
+int sspp_chain_contacts_host(const sspp_chain* c, const double* q, int64_t N, uint8_t* hit);
+int sspp_chain_score_ctrl_host(sspp_chain* c, const double* knots, int degree, const double* ctrl /* [B][n][dof] */,
+                               int64_t B, int n, int W, int with_collision, double* arc_out, uint8_t* feasible_out,
+                               sspp_best* best_out);
+int sspp_chain_plan_host(sspp_chain* c, const double* start, const double* end, double sigma, const double* limits,
+                         int sample_count, int check_points, int init_points, uint64_t seed, double* knots_out,
+                         double* ctrl_out /* [sample_count][init_points][dof] */, uint8_t* feasible_out,
+                         double* arc_out, sspp_best* best_out);
 
 /* ---- splines (host) ---- */
 int sspp_interpolate(const double* pts /* [n][D] */, int n, int D, int degree,

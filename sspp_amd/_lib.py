@@ -55,6 +55,20 @@ class PairInfo(C.Structure):
                 ("margin", C.c_double)]
 
 
+class JointView(C.Structure):
+    _fields_ = [("njnt", C.c_int), ("jnt_type", C.POINTER(C.c_int32)), ("jnt_body", C.POINTER(C.c_int32)),
+                ("jnt_qpos_adr", C.POINTER(C.c_int32)), ("jnt_axis", C.POINTER(C.c_double)),
+                ("jnt_pos", C.POINTER(C.c_double)), ("nq", C.c_int), ("qpos0", C.POINTER(C.c_double))]
+
+
+class ChainInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("dof", "n_driven_bodies", "n_geoms", "n_moving_geoms", "n_static_geoms",
+                                       "n_pairs", "n_static_pairs", "static_contacts")]
+
+
+CHAIN_MAX_BODIES, CHAIN_MAX_DOF, CHAIN_MAX_PAIRS = 16, 16, 512
+
+
 class SsppArgs(C.Structure):
     _fields_ = [("knots", C.POINTER(C.c_double)), ("degree", C.c_int),
                 ("init_ctrl", C.POINTER(C.c_double)), ("n_ctrl", C.c_int), ("dof", C.c_int),
@@ -128,6 +142,23 @@ SIGNATURES = {
     "sspp_job_path_contacts": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "sspp_scene_contacts_host": (C.c_int, [_vp, _d, _i64, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "sspp_path_contacts_host": (C.c_int, [_vp, _d, _i, _d, _i64, _i, _i, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "sspp_model_load_mjcf_joints": (C.c_int, [C.c_char_p, C.POINTER(_vp)]),
+    "sspp_model_joints_get": (C.c_int, [_vp, C.POINTER(JointView)]),
+    "sspp_model_joint_name": (C.c_char_p, [_vp, _i]),
+    "sspp_chain_create": (C.c_int, [_vp, _i, _i, C.POINTER(_vp)]),
+    "sspp_chain_get_info": (C.c_int, [_vp, C.POINTER(ChainInfo)]),
+    "sspp_chain_free": (None, [_vp]),
+    "sspp_chain_pairs": (C.c_int, [_vp, C.POINTER(PairInfo), _i, C.POINTER(C.c_int)]),
+    "sspp_chain_fk": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "sspp_chain_contacts": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    "sspp_chain_score_ctrl": (C.c_int, [_vp, _d, _i, _vp, _i64, _i64, _i, _i, _vp, _vp, _vp, _vp]),
+    "sspp_chain_sample_score": (C.c_int, [_vp, _d, _i, _d, _i, _i, C.c_double, _d, C.c_uint64, _i64, _i64, _vp,
+                                          _vp, _vp, _vp, _vp]),
+    "sspp_chain_contacts_host": (C.c_int, [_vp, _d, _i64, C.POINTER(C.c_uint8)]),
+    "sspp_chain_score_ctrl_host": (C.c_int, [_vp, _d, _i, _d, _i64, _i, _i, _i, _d, C.POINTER(C.c_uint8),
+                                             C.POINTER(Best)]),
+    "sspp_chain_plan_host": (C.c_int, [_vp, _d, _d, C.c_double, _d, _i, _i, _i, C.c_uint64, _d, _d,
+                                       C.POINTER(C.c_uint8), _d, C.POINTER(Best)]),
     "sspp_interpolate": (C.c_int, [_d, _i, _i, _i, _d, _d, _d]),
     "sspp_spline_eval": (C.c_int, [_d, _i, _i, _d, _i, C.c_double, _d]),
     "sspp_job_create_sspp": (C.c_int, [_vp, C.POINTER(SsppArgs), _i64, C.POINTER(_vp)]),

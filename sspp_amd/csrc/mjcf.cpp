@@ -5,7 +5,13 @@
 // Semantics follow MuJoCo's compiler for what the shipped scenes contain:
 //   * bodies depth-first pre-order, world body 0, geoms ordered body by body;
 //   * <freejoint/> or <joint type="free"/> -> 7 qpos each, qpos0 = (pos, normalised quat);
-//     any other joint type is rejected (SSPP_E_UNSUPPORTED) — hinge chains are out of scope;
+//     sspp_model_load_mjcf rejects every other joint type (SSPP_E_UNSUPPORTED);
+//   * sspp_model_load_mjcf_joints (load_mjcf's joints = true) also accepts <joint type="hinge|slide">,
+//     several per body in document order: 1 qpos each, `axis` (default 0 0 1) normalised (zero:
+//     SSPP_E_SCENE), `pos` (default 0 0 0), `ref` -> qpos0 (a hinge's in the compiler's angle unit, a
+//     slide's in metres); every other joint attribute (range, limited, damping, ...) is ignored; a ball
+//     joint stays SSPP_E_UNSUPPORTED; a free joint beside other joints on one body is SSPP_E_SCENE;
+//     joint attributes resolve through <default><joint/> classes and childclass as a geom's do;
 //   * nested <default class=...> with inheritance; element class = `class` attribute, else the
 //     innermost enclosing body's `childclass`, else "main"; explicit attributes win;
 //   * orientation from quat / euler (<compiler angle eulerseq>) / axisangle, normalised;
@@ -137,8 +143,9 @@ struct Loader {
     struct GeomTmp { std::string name; int type; double size[3], pos[3], quat[4]; int ct, ca; double margin; int body; };
     std::vector<GeomTmp> geoms;
     int nq = 0;
+    bool joints = false;  // hinge and slide joints are accepted (sspp_model_load_mjcf_joints)
 
-    explicit Loader(sspp_model& mm) : m(mm) {}
+    Loader(sspp_model& mm, bool jj) : m(mm), joints(jj) {}
 
     AttrMap attrs_of(const XNode& n, const std::string& childclass) {
         auto c = n.get("class");
@@ -203,21 +210,51 @@ struct Loader {
                 std::string ncc = chc ? *chc : cc;
                 int bid = m.nbody();
                 int jnt = -1, adr = -1;
+                const int jnt_adr = m.njnt();
+                std::vector<double> scalar_ref;  // this body's hinge / slide reference values
                 for (auto& jp : k.kids) {
                     std::string jt;
+                    AttrMap ja;
                     if (jp->tag == "freejoint") jt = "free";
                     else if (jp->tag == "joint") {
-                        auto tt = jp->get("type");
-                        if (tt) jt = *tt;
-                        else {
-                            auto c = jp->get("class");
-                            AttrMap da = dfl.resolve(c ? *c : ncc, "joint");
-                            jt = da.count("type") ? da["type"] : "hinge";
-                        }
+                        ja = attrs_of(*jp, ncc);
+                        jt = ja.count("type") ? ja["type"] : "hinge";
                     } else continue;
-                    if (jt != "free") throw std::runtime_error("unsupported joint type '" + jt + "'");
-                    if (jnt == 0) throw std::runtime_error("body with two free joints");
-                    jnt = 0; adr = nq; nq += 7;
+                    const std::string jname = (jp->tag == "joint" && ja.count("name")) ? ja["name"]
+                                              : (jp->get("name") ? *jp->get("name") : std::string());
+                    const bool scalar = joints && (jt == "hinge" || jt == "slide");
+                    if (jt != "free" && !scalar) throw std::runtime_error("unsupported joint type '" + jt + "'");
+                    if (jnt == 0 && !scalar) throw std::runtime_error("body with two free joints");
+                    if ((jnt == 0) != (jt == "free") && jnt != -1)
+                        throw std::runtime_error("body '" + (k.get("name") ? *k.get("name") : std::string()) +
+                                                 "': a free joint mixed with other joints");
+                    m.jnt_names.push_back(jname);
+                    m.jnt_body.push_back(bid);
+                    m.jnt_qpos_adr.push_back(nq);
+                    if (!scalar) {
+                        jnt = 0; adr = nq; nq += 7;
+                        m.jnt_type.push_back(0);
+                        m.jnt_axis.insert(m.jnt_axis.end(), {0.0, 0.0, 1.0});
+                        m.jnt_pos.insert(m.jnt_pos.end(), {0.0, 0.0, 0.0});
+                        continue;
+                    }
+                    // hinge / slide: axis (default 0 0 1) normalised, pos (default 0 0 0) in the
+                    // body's frame, ref -> qpos0 (a hinge's in the compiler's angle unit)
+                    const int code = jt == "slide" ? 2 : 3;
+                    auto ax = floats(ja.count("axis") ? ja["axis"] : "0 0 1");
+                    auto jp3 = floats(ja.count("pos") ? ja["pos"] : "0 0 0");
+                    if (ax.size() != 3 || jp3.size() != 3)
+                        throw std::runtime_error("joint '" + jname + "': axis and pos need 3 numbers");
+                    const double an = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
+                    if (!(an > 0.0)) throw std::runtime_error("joint '" + jname + "': zero axis");
+                    double ref = ja.count("ref") ? std::stod(ja["ref"]) : 0.0;
+                    if (code == 3 && comp.degree) ref = ref * M_PI / 180.0;
+                    if (jnt == -1) { jnt = code; adr = nq; }
+                    m.jnt_type.push_back(code);
+                    for (int j = 0; j < 3; ++j) m.jnt_axis.push_back(ax[j] / an);
+                    for (int j = 0; j < 3; ++j) m.jnt_pos.push_back(jp3[j]);
+                    scalar_ref.push_back(ref);
+                    nq += 1;
                 }
                 AttrMap ba;
                 for (auto& kv : k.attrs) ba[kv.first] = kv.second;
@@ -235,6 +272,9 @@ struct Loader {
                     for (int j = 0; j < 3; ++j) m.qpos0.push_back(ps[j]);
                     for (int j = 0; j < 4; ++j) m.qpos0.push_back(q[j]);
                 }
+                m.qpos0.insert(m.qpos0.end(), scalar_ref.begin(), scalar_ref.end());
+                m.body_jnt_adr.push_back(jnt_adr);
+                m.body_jnt_num.push_back(m.njnt() - jnt_adr);
                 walk(k, bid, ncc);
             } else if (k.tag == "frame" || k.tag == "replicate" || k.tag == "attach") {
                 throw std::runtime_error("unsupported MJCF element <" + k.tag + ">");
@@ -261,6 +301,8 @@ struct Loader {
         m.body_parent.push_back(-1);
         m.body_jnt_type.push_back(-1);
         m.body_qpos_adr.push_back(-1);
+        m.body_jnt_adr.push_back(0);
+        m.body_jnt_num.push_back(0);
         for (int j = 0; j < 3; ++j) m.body_pos.push_back(0.0);
         m.body_quat.insert(m.body_quat.end(), {1.0, 0.0, 0.0, 0.0});
         for (auto& k : root.kids)
@@ -301,7 +343,7 @@ struct Loader {
 
 }  // namespace
 
-int load_mjcf(const std::string& path, sspp_model& out) {
+int load_mjcf(const std::string& path, sspp_model& out, bool joints) {
     std::ifstream f(path, std::ios::binary);
     if (!f) return set_error(SSPP_E_IO, "Failed to load MJCF model: cannot open '" + path + "'");
     std::stringstream ss;
@@ -312,7 +354,7 @@ int load_mjcf(const std::string& path, sspp_model& out) {
         auto root = rd.parse();
         sspp_model m;
         m.path = path;
-        Loader L(m);
+        Loader L(m, joints);
         L.run(*root);
         out = std::move(m);
     } catch (const std::exception& e) {

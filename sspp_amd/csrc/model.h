@@ -16,8 +16,23 @@ struct sspp_model {
     std::vector<double> geom_size, geom_pos, geom_quat, geom_margin;
     std::vector<int32_t> exclude;
     std::vector<double> qpos0;
+    // joints, in body pre-order and document order within a body (every loader fills them; only
+    // sspp_model_load_mjcf_joints lets a hinge or a slide in).  Types are MuJoCo's mjtJoint codes:
+    // 0 free (7 qpos), 2 slide, 3 hinge (1 qpos each); axis (normalised) and pos are in the body's
+    // frame; a scalar joint's reference value is qpos0[jnt_qpos_adr]
+    std::vector<std::string> jnt_names;
+    std::vector<int32_t> jnt_type, jnt_body, jnt_qpos_adr;
+    std::vector<double> jnt_axis, jnt_pos;
+    std::vector<int32_t> body_jnt_adr, body_jnt_num;  // a body's joints: [adr, adr + num)
     int nbody() const { return (int)body_parent.size(); }
     int ngeom() const { return (int)geom_type.size(); }
+    int njnt() const { return (int)jnt_type.size(); }
+    // the first hinge or slide joint, -1 for a model of free and jointless bodies
+    int first_scalar_joint() const {
+        for (int j = 0; j < njnt(); ++j)
+            if (jnt_type[j] != 0) return j;
+        return -1;
+    }
 };
 
 namespace sspp {
@@ -26,7 +41,8 @@ int set_error(int code, const std::string& msg);
 void clear_error();
 
 // MJCF -> model (mjcf.cpp)
-int load_mjcf(const std::string& path, sspp_model& out);
+// joints = true also accepts <joint type="hinge|slide"> (sspp_model_load_mjcf_joints)
+int load_mjcf(const std::string& path, sspp_model& out, bool joints = false);
 // the loader's quaternion normalisation (body quat, qpos0): q / |q|, the identity for |q| = 0.  A
 // scene update (sspp_scene_set_qpos) normalises with the same operations, so that a re-posed
 // scene holds the bits a scene loaded from a file with those values holds

@@ -35,6 +35,37 @@ int sspp_model_load_mjcf(const char* xml_path, sspp_model** out) {
     return SSPP_OK;
 }
 
+int sspp_model_load_mjcf_joints(const char* xml_path, sspp_model** out) {
+    sspp::clear_error();
+    if (!xml_path || !out) return sspp::set_error(SSPP_E_INVAL, "sspp_model_load_mjcf_joints: null argument");
+    auto* m = new sspp_model();
+    int rc = sspp::load_mjcf(xml_path, *m, true);
+    if (rc != SSPP_OK) {
+        delete m;
+        return rc;
+    }
+    *out = m;
+    return SSPP_OK;
+}
+
+int sspp_model_joints_get(const sspp_model* m, sspp_joint_view* v) {
+    if (!m || !v) return sspp::set_error(SSPP_E_INVAL, "null argument");
+    v->njnt = m->njnt();
+    v->jnt_type = m->jnt_type.data();
+    v->jnt_body = m->jnt_body.data();
+    v->jnt_qpos_adr = m->jnt_qpos_adr.data();
+    v->jnt_axis = m->jnt_axis.data();
+    v->jnt_pos = m->jnt_pos.data();
+    v->nq = (int)m->qpos0.size();
+    v->qpos0 = m->qpos0.data();
+    return SSPP_OK;
+}
+
+const char* sspp_model_joint_name(const sspp_model* m, int joint) {
+    if (!m || joint < 0 || joint >= m->njnt()) return nullptr;
+    return m->jnt_names[joint].c_str();
+}
+
 int sspp_model_view_get(const sspp_model* m, sspp_model_view* v) {
     if (!m || !v) return sspp::set_error(SSPP_E_INVAL, "null argument");
     v->nbody = m->nbody();

@@ -1,0 +1,440 @@
+// sspp_chain.hip — articulated movers: the chain's kernels, launches and C ABI (DESIGN.md §5
+// "Articulated movers").
+//
+// A translation unit of its own: no scoring kernel is instantiated here, so none is rebuilt.  The
+// kernels are thin loops around sspc::chain_fk / geom_pose / chain_contact (sspp_chain.h).  A lane
+// holds one pose; its driven bodies' frames live in dynamic LDS laid out [slot][component][lane]
+// (consecutive lanes, consecutive 8-byte words; sized from the chain's driven-body count), so no
+// per-lane array is indexed at run time.  The body, joint and pair loops are wave-uniform: records
+// are scalar loads and the type branches are uniform.
+//   k_chain_fk        lane = pose: every geom's world pose
+//   k_chain_contacts  lane = pose: one byte
+//   k_chain_feas      one wave per candidate, lanes = waypoints in passes of 64 with a wave vote
+//                     after each pass: a candidate stops at its first contact (checkCollision's
+//                     semantics, no atomics).  A waypoint's coordinates are evaluated when a joint
+//                     asks for them, with eval_pt's products and fma order
+//   k_chain_best      findBestPath over the batch: lowest arc, lowest id on ties, the feasible count
+// Arc lengths and sampled candidates come from a scene-less SamplingPathPlanner job (k_sspp_c2f,
+// arc_all = 1): the existing code, bit for bit.
+#include "sspp_chain.h"
+
+using namespace sspk;
+using namespace sspc;
+
+namespace sspc {
+
+constexpr int kChainBlock = 64;  // one wave: the frames' LDS is per lane, nothing is shared
+
+struct ChainT {
+    const CBody* __restrict__ bodies;
+    const CJoint* __restrict__ joints;
+    const CGeom* __restrict__ geoms;
+    const CPair* __restrict__ pairs;
+    int nd, ng, np, D;
+};
+
+struct LdsFrames {
+    double* base;  // + lane
+    __device__ __forceinline__ double get(int slot, int c) const { return base[(slot * 7 + c) * kChainBlock]; }
+    __device__ __forceinline__ void set(int slot, int c, double v) const { base[(slot * 7 + c) * kChainBlock] = v; }
+};
+
+inline size_t chain_lds(int nd) { return sizeof(double) * 7 * kChainBlock * (size_t)std::max(1, nd); }
+
+__global__ __launch_bounds__(kChainBlock) void k_chain_fk(const ChainT T, const double* __restrict__ d_q,
+                                                           const long long N, double* __restrict__ gpos,
+                                                           double* __restrict__ gmat) {
+    extern __shared__ double s_fr[];
+    const long long i = (long long)blockIdx.x * kChainBlock + threadIdx.x;
+    if (i >= N) return;  // (nothing below votes or synchronises)
+    const LdsFrames fr{s_fr + threadIdx.x};
+    const double* q = d_q + i * T.D;
+    chain_fk((cbody_t)T.bodies, (cjoint_t)T.joints, T.nd, T.D, [q](int adr) { return q[adr]; }, fr);
+    for (int g = 0; g < T.ng; ++g) {
+        double p[3], m[9];
+        geom_pose((ccgeom_t)T.geoms + g, fr, p, m);
+        double* op = gpos + ((size_t)i * T.ng + g) * 3;
+        double* om = gmat + ((size_t)i * T.ng + g) * 9;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) op[k] = p[k];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) om[k] = m[k];
+    }
+}
+
+__global__ __launch_bounds__(kChainBlock) void k_chain_contacts(const ChainT T, const int static_block,
+                                                                 const double* __restrict__ d_q, const long long N,
+                                                                 uint8_t* __restrict__ hit) {
+    extern __shared__ double s_fr[];
+    const long long i = (long long)blockIdx.x * kChainBlock + threadIdx.x;
+    if (i >= N) return;
+    const LdsFrames fr{s_fr + threadIdx.x};
+    const double* q = d_q + i * T.D;
+    chain_fk((cbody_t)T.bodies, (cjoint_t)T.joints, T.nd, T.D, [q](int adr) { return q[adr]; }, fr);
+    const int h = chain_contact((ccgeom_t)T.geoms, (ccpair_t)T.pairs, T.np, fr);
+    hit[i] = (uint8_t)((h || static_block) ? 1 : 0);
+}
+
+// One wave per candidate b: waypoint i = pass * 64 + lane at u = i / W, from the job's basis rows
+// (tab: P + 1 values per waypoint, span: its knot span).  Writes feasible[b], and +inf over an
+// infeasible candidate's arc length.
+__global__ __launch_bounds__(kChainBlock) void k_chain_feas(const ChainT T, const int static_block, const int P,
+                                                             const int n, const int W,
+                                                             const double* __restrict__ tab,
+                                                             const int* __restrict__ span,
+                                                             const double* __restrict__ ctrl,
+                                                             double* __restrict__ arc,
+                                                             uint8_t* __restrict__ feasible) {
+    extern __shared__ double s_fr[];
+    const long long b = blockIdx.x;
+    const int lane = threadIdx.x;
+    const LdsFrames fr{s_fr + lane};
+    const int D = T.D;
+    bool blocked = static_block != 0;
+    for (int base = 0; base <= W && !blocked; base += kChainBlock) {
+        const int i = base + lane;
+        int h = 0;
+        if (i <= W) {
+            const double* N = tab + (size_t)i * (P + 1);
+            double Nr[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Nr[r] = r <= P ? N[r] : 0.0;
+            const double* c0 = ctrl + (size_t)b * n * D + (size_t)(span[i] - P) * D;
+            // eval_pt's products and fma order for coordinate adr
+            auto qv = [&](int adr) {
+                double acc = Nr[0] * c0[adr];
+#pragma unroll
+                for (int r = 1; r <= 3; ++r)
+                    if (r <= P) acc = fma(Nr[r], c0[r * D + adr], acc);
+                return acc;
+            };
+            chain_fk((cbody_t)T.bodies, (cjoint_t)T.joints, T.nd, D, qv, fr);
+            h = chain_contact((ccgeom_t)T.geoms, (ccpair_t)T.pairs, T.np, fr);
+        }
+        blocked = __any(h) != 0;  // wave-uniform: every lane leaves the loop together
+    }
+    if (lane == 0) {
+        feasible[b] = blocked ? 0 : 1;
+        if (blocked) arc[b] = INFINITY;
+    }
+}
+
+// findBestPath over B candidates in one workgroup: (arc, id) minimum over the feasible ones
+constexpr int kBestBlock = 256;
+__global__ __launch_bounds__(kBestBlock) void k_chain_best(const double* __restrict__ arc,
+                                                            const uint8_t* __restrict__ feasible, const long long B,
+                                                            const long long first_id, sspp_best* __restrict__ out) {
+    __shared__ double s_c[kBestBlock];
+    __shared__ long long s_i[kBestBlock], s_n[kBestBlock];
+    double bc = INFINITY;
+    long long bi = -1, cnt = 0;
+    for (long long k = threadIdx.x; k < B; k += kBestBlock) {
+        if (!feasible[k]) continue;
+        ++cnt;
+        const double a = arc[k];
+        if (a < bc) { bc = a; bi = k; }  // (ascending k per thread: the lowest id of equal arcs stays)
+    }
+    s_c[threadIdx.x] = bc; s_i[threadIdx.x] = bi; s_n[threadIdx.x] = cnt;
+    __syncthreads();
+    for (int s = kBestBlock / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            const double oc = s_c[threadIdx.x + s];
+            const long long oi = s_i[threadIdx.x + s];
+            if (oi >= 0 && (s_i[threadIdx.x] < 0 || oc < s_c[threadIdx.x] ||
+                            (oc == s_c[threadIdx.x] && oi < s_i[threadIdx.x]))) {
+                s_c[threadIdx.x] = oc;
+                s_i[threadIdx.x] = oi;
+            }
+            s_n[threadIdx.x] += s_n[threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out->cost = s_i[0] >= 0 ? s_c[0] : INFINITY;
+        out->index = s_i[0] >= 0 ? first_id + s_i[0] : -1;
+        out->count = s_n[0];
+        out->reserved = 0;
+    }
+}
+
+}  // namespace sspc
+
+struct sspp_chain {
+    ChainTables t;
+    int count_static = 0;
+    int device = 0;
+    Dev<CBody> d_bodies;
+    Dev<CJoint> d_joints;
+    Dev<CGeom> d_geoms;
+    Dev<CPair> d_pairs;
+    // the scene-less job of the last spline shape (arc lengths, sampled candidates), the candidates
+    // of a sample_score call without d_ctrl_out, and the job's own argmin record (not the chain's)
+    sspp_job* job = nullptr;
+    std::vector<double> job_knots;
+    int job_p = 0, job_n = 0, job_W = 0;
+    int64_t job_cap = 0;
+    Dev<double> d_ctrl;
+    Dev<sspp_best> d_jobbest;
+    ~sspp_chain() {
+        if (job) sspp_job_free(job);
+    }
+    int static_block() const { return (count_static && t.static_contacts > 0) ? 1 : 0; }
+    ChainT view() const {
+        return ChainT{d_bodies.p, d_joints.p, d_geoms.p, d_pairs.p, (int)t.bodies.size(), (int)t.geoms.size(),
+                      (int)t.pairs.size(), t.D};
+    }
+};
+
+extern "C" int sspp_chain_create(const sspp_model* m, int dof, int count_static, sspp_chain** out) {
+    sspp::clear_error();
+    if (!m || !out) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_create: null argument");
+    if ((int)m->body_jnt_adr.size() != m->nbody())
+        return sspp::set_error(SSPP_E_INVAL, "sspp_chain_create: the model has no joint tables");
+    auto* c = new sspp_chain();
+    int rc = chain_build(*m, dof, c->t);
+    c->count_static = count_static;
+    if (!rc) (void)hipGetDevice(&c->device);
+    if (rc || (rc = c->d_bodies.upload(c->t.bodies.data(), c->t.bodies.size())) ||
+        (rc = c->d_joints.upload(c->t.joints.data(), c->t.joints.size())) ||
+        (rc = c->d_geoms.upload(c->t.geoms.data(), c->t.geoms.size())) ||
+        (rc = c->d_pairs.upload(c->t.pairs.data(), c->t.pairs.size())) || (rc = c->d_jobbest.reserve(1))) {
+        delete c;
+        return rc;
+    }
+    *out = c;
+    return SSPP_OK;
+}
+
+extern "C" void sspp_chain_free(sspp_chain* c) { delete c; }
+
+extern "C" int sspp_chain_get_info(const sspp_chain* c, sspp_chain_info* out) {
+    if (!c || !out) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_get_info: null argument");
+    out->dof = c->t.D;
+    out->n_driven_bodies = (int)c->t.bodies.size();
+    out->n_geoms = (int)c->t.geoms.size();
+    out->n_moving_geoms = c->t.n_moving_geoms;
+    out->n_static_geoms = c->t.n_static_geoms;
+    out->n_pairs = (int)c->t.pairs.size();
+    out->n_static_pairs = c->t.n_static_pairs;
+    out->static_contacts = c->t.static_contacts;
+    return SSPP_OK;
+}
+
+extern "C" int sspp_chain_pairs(const sspp_chain* c, sspp_pair_info* out, int cap, int* n) {
+    sspp::clear_error();
+    if (!c || !n) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_pairs: null argument");
+    *n = (int)c->t.pairs.size();
+    if (!out) return SSPP_OK;
+    if (cap < *n)
+        return sspp::set_error(SSPP_E_INVAL, "sspp_chain_pairs: cap = " + std::to_string(cap) + " < " +
+                                                 std::to_string(*n) + " pairs");
+    for (int k = 0; k < *n; ++k) {
+        const CPair& p = c->t.pairs[k];
+        const int g1 = std::min(p.a, p.b), g2 = std::max(p.a, p.b);
+        out[k] = sspp_pair_info{g1, g2, c->t.geoms[g1].slot >= 0, c->t.geoms[g2].slot >= 0, p.margin};
+    }
+    return SSPP_OK;
+}
+
+static int chain_blocks(int64_t items, int* out) {
+    const int64_t nblk = (items + kChainBlock - 1) / kChainBlock;
+    if (nblk > 0x7fffffffll) return sspp::set_error(SSPP_E_INVAL, "sspp_chain: too many poses for one launch");
+    *out = (int)nblk;
+    return SSPP_OK;
+}
+
+extern "C" int sspp_chain_fk(const sspp_chain* c, const double* d_q, int64_t N, double* d_gpos, double* d_gmat,
+                             void* stream) {
+    sspp::clear_error();
+    if (!c) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_fk: null chain");
+    if (N < 0) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_fk: negative pose count");
+    if (N == 0 || c->t.geoms.empty()) return SSPP_OK;
+    if (!d_q || !d_gpos || !d_gmat) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_fk: null poses / output");
+    int nblk = 0;
+    if (int rc = chain_blocks(N, &nblk)) return rc;
+    const ChainT T = c->view();
+    hipLaunchKernelGGL(k_chain_fk, dim3(nblk), dim3(kChainBlock), chain_lds(T.nd), (hipStream_t)stream, T, d_q,
+                       (long long)N, d_gpos, d_gmat);
+    return sspo::hip_fail(hipGetLastError(), "sspp_chain_fk launch");
+}
+
+extern "C" int sspp_chain_contacts(const sspp_chain* c, const double* d_q, int64_t N, uint8_t* d_hit, void* stream) {
+    sspp::clear_error();
+    if (!c) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_contacts: null chain");
+    if (N < 0) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_contacts: negative pose count");
+    if (N == 0) return SSPP_OK;
+    if (!d_q || !d_hit) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_contacts: null poses / output");
+    int nblk = 0;
+    if (int rc = chain_blocks(N, &nblk)) return rc;
+    const ChainT T = c->view();
+    hipLaunchKernelGGL(k_chain_contacts, dim3(nblk), dim3(kChainBlock), chain_lds(T.nd), (hipStream_t)stream, T,
+                       c->static_block(), d_q, (long long)N, d_hit);
+    return sspo::hip_fail(hipGetLastError(), "sspp_chain_contacts launch");
+}
+
+// the scene-less job for splines of this shape (created or replaced on a new shape or a larger
+// batch: synchronous; otherwise nothing is allocated)
+static int chain_job(sspp_chain* c, const double* knots, int degree, int n, int W, int64_t B) {
+    const int D = c->t.D;
+    if (!knots) return sspp::set_error(SSPP_E_INVAL, "sspp_chain: null knots");
+    if (degree < 2 || degree > 3 || n < degree + 1)
+        return sspp::set_error(degree < 2 || degree > 3 ? SSPP_E_UNSUPPORTED : SSPP_E_INVAL,
+                               "sspp_chain: spline degree 2 or 3 with at least degree + 1 control points");
+    const size_t nk = (size_t)n + degree + 1;
+    if (c->job && c->job_p == degree && c->job_n == n && c->job_W == W && c->job_cap >= B &&
+        c->job_knots.size() == nk && std::memcmp(c->job_knots.data(), knots, sizeof(double) * nk) == 0)
+        return SSPP_OK;
+    if (c->job) {
+        (void)hipDeviceSynchronize();  // (a launch may still read the older job's tables)
+        sspp_job_free(c->job);
+        c->job = nullptr;
+    }
+    const std::vector<double> zeros((size_t)n * D, 0.0), ones((size_t)D, 1.0);
+    sspp_sspp_args a{};
+    a.knots = knots; a.degree = degree; a.init_ctrl = zeros.data(); a.n_ctrl = n; a.dof = D;
+    a.sigma = 0.0; a.limits = ones.data(); a.check_points = W; a.seed = 0; a.arc_all = 1;
+    const int64_t cap = std::max<int64_t>(B, 1024);
+    int rc = sspp_job_create_sspp(nullptr, &a, cap, &c->job);
+    if (rc) return rc;
+    c->job_knots.assign(knots, knots + nk);
+    c->job_p = degree; c->job_n = n; c->job_W = W; c->job_cap = cap;
+    return SSPP_OK;
+}
+
+// feasibility of the candidates in d_ctrl over the job's arcs, then the argmin
+static int chain_finish(sspp_chain* c, const double* d_ctrl, int64_t first_id, int64_t B, double* d_arc,
+                        uint8_t* d_feasible, sspp_best* d_best, hipStream_t st) {
+    if (B > 0x7fffffffll) return sspp::set_error(SSPP_E_INVAL, "sspp_chain: too many candidates for one launch");
+    const ChainT T = c->view();
+    const sspp_job* j = c->job;
+    hipLaunchKernelGGL(k_chain_feas, dim3((int)B), dim3(kChainBlock), chain_lds(T.nd), st, T, c->static_block(), j->p,
+                       j->n, j->W, j->d_tab.p, j->d_span.p, d_ctrl, d_arc, d_feasible);
+    if (int rc = sspo::hip_fail(hipGetLastError(), "k_chain_feas launch")) return rc;
+    if (d_best) {
+        hipLaunchKernelGGL(k_chain_best, dim3(1), dim3(kBestBlock), 0, st, d_arc, d_feasible, (long long)B,
+                           (long long)first_id, d_best);
+        return sspo::hip_fail(hipGetLastError(), "k_chain_best launch");
+    }
+    return SSPP_OK;
+}
+
+extern "C" int sspp_chain_score_ctrl(sspp_chain* c, const double* knots, int degree, const double* d_ctrl,
+                                     int64_t first_id, int64_t B, int n, int W, double* d_arc, uint8_t* d_feasible,
+                                     sspp_best* d_best, void* stream) {
+    sspp::clear_error();
+    if (!c) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_score_ctrl: null chain");
+    if (B < 0) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_score_ctrl: negative batch");
+    if (B == 0) return SSPP_OK;
+    if (!d_ctrl || !d_arc || !d_feasible) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_score_ctrl: null argument");
+    int rc;
+    if ((rc = chain_job(c, knots, degree, n, W, B)) ||
+        (rc = sspp_job_score_ctrl(c->job, d_ctrl, first_id, B, d_arc, d_feasible, c->d_jobbest.p, stream)))
+        return rc;
+    return chain_finish(c, d_ctrl, first_id, B, d_arc, d_feasible, d_best, (hipStream_t)stream);
+}
+
+extern "C" int sspp_chain_sample_score(sspp_chain* c, const double* knots, int degree, const double* init_ctrl, int n,
+                                       int W, double sigma, const double* limits, uint64_t seed, int64_t first_id,
+                                       int64_t B, double* d_arc, uint8_t* d_feasible, double* d_ctrl_out,
+                                       sspp_best* d_best, void* stream) {
+    sspp::clear_error();
+    if (!c) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_sample_score: null chain");
+    if (B < 0) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_sample_score: negative batch");
+    if (B == 0) return SSPP_OK;
+    if (!init_ctrl || !limits || !d_arc || !d_feasible)
+        return sspp::set_error(SSPP_E_INVAL, "sspp_chain_sample_score: null argument");
+    int rc;
+    if ((rc = chain_job(c, knots, degree, n, W, B))) return rc;
+    if (!d_ctrl_out) {  // the feasibility kernel reads the candidates: keep them in the chain's buffer
+        if ((rc = c->d_ctrl.reserve((size_t)c->job_cap * n * c->t.D))) return rc;
+        d_ctrl_out = c->d_ctrl.p;
+    }
+    if ((rc = sspp_job_update_sspp(c->job, init_ctrl, sigma, limits, seed, stream)) ||
+        (rc = sspp_job_sample_score(c->job, first_id, B, d_arc, d_feasible, d_ctrl_out, c->d_jobbest.p, stream)))
+        return rc;
+    return chain_finish(c, d_ctrl_out, first_id, B, d_arc, d_feasible, d_best, (hipStream_t)stream);
+}
+
+// ---- the same on host buffers (the drop-in planner of an articulated model): staged to the device,
+// run by the calls above and copied back on the drop-in planners' shared stream, which alone is waited for
+extern "C" int sspp_chain_contacts_host(const sspp_chain* c, const double* q, int64_t N, uint8_t* hit) {
+    sspp::clear_error();
+    if (!c || !q || !hit || N < 1) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_contacts_host: bad argument");
+    hipStream_t st = (hipStream_t)sspp::shared_stream(0);
+    const size_t nq = (size_t)N * c->t.D;
+    Dev<double> d_q;
+    Dev<uint8_t> d_h;
+    int rc;
+    if ((rc = d_q.reserve(nq)) || (rc = d_h.reserve((size_t)N))) return rc;
+    rc = hip_fail(hipMemcpyAsync(d_q.p, q, sizeof(double) * nq, hipMemcpyHostToDevice, st), "copy poses");
+    if (!rc) rc = sspp_chain_contacts(c, d_q.p, N, d_h.p, st);
+    if (!rc) rc = hip_fail(hipMemcpyAsync(hit, d_h.p, (size_t)N, hipMemcpyDeviceToHost, st), "copy hits");
+    const int rs = hip_fail(hipStreamSynchronize(st), "sspp_chain_contacts_host");
+    return rc ? rc : rs;
+}
+
+static int chain_read_back(hipStream_t st, int rc, int64_t B, const Dev<double>& d_arc, const Dev<uint8_t>& d_f,
+                           const Dev<sspp_best>& d_b, double* arc_out, uint8_t* feasible_out, sspp_best* best_out) {
+    if (!rc && arc_out) rc = hip_fail(hipMemcpyAsync(arc_out, d_arc.p, sizeof(double) * B, hipMemcpyDeviceToHost, st), "copy arc");
+    if (!rc && feasible_out) rc = hip_fail(hipMemcpyAsync(feasible_out, d_f.p, (size_t)B, hipMemcpyDeviceToHost, st), "copy feasible");
+    if (!rc && best_out) rc = hip_fail(hipMemcpyAsync(best_out, d_b.p, sizeof(sspp_best), hipMemcpyDeviceToHost, st), "copy best");
+    const int rs = hip_fail(hipStreamSynchronize(st), "sspp_chain host call");
+    return rc ? rc : rs;
+}
+
+extern "C" int sspp_chain_score_ctrl_host(sspp_chain* c, const double* knots, int degree, const double* ctrl, int64_t B,
+                                          int n, int W, int with_collision, double* arc_out, uint8_t* feasible_out,
+                                          sspp_best* best_out) {
+    sspp::clear_error();
+    if (!c || !knots || !ctrl || B < 1) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_score_ctrl_host: bad argument");
+    hipStream_t st = (hipStream_t)sspp::shared_stream(0);
+    const size_t nc = (size_t)B * n * c->t.D;
+    Dev<double> d_ctrl, d_arc;
+    Dev<uint8_t> d_f;
+    Dev<sspp_best> d_b;
+    int rc;
+    if ((rc = d_ctrl.reserve(nc)) || (rc = d_arc.reserve((size_t)B)) || (rc = d_f.reserve((size_t)B)) ||
+        (rc = d_b.reserve(1)))
+        return rc;
+    rc = hip_fail(hipMemcpyAsync(d_ctrl.p, ctrl, sizeof(double) * nc, hipMemcpyHostToDevice, st), "copy splines");
+    if (!rc && with_collision) rc = sspp_chain_score_ctrl(c, knots, degree, d_ctrl.p, 0, B, n, W, d_arc.p, d_f.p, d_b.p, st);
+    if (!rc && !with_collision && !(rc = chain_job(c, knots, degree, n, W, B)))
+        rc = sspp_job_score_ctrl(c->job, d_ctrl.p, 0, B, d_arc.p, d_f.p, d_b.p, st);
+    return chain_read_back(st, rc, B, d_arc, d_f, d_b, arc_out, feasible_out, best_out);
+}
+
+extern "C" int sspp_chain_plan_host(sspp_chain* c, const double* start, const double* end, double sigma,
+                                    const double* limits, int sample_count, int check_points, int init_points,
+                                    uint64_t seed, double* knots_out, double* ctrl_out, uint8_t* feasible_out,
+                                    double* arc_out, sspp_best* best_out) {
+    sspp::clear_error();
+    if (!c || !start || !end || !limits || !knots_out)
+        return sspp::set_error(SSPP_E_INVAL, "sspp_chain_plan_host: null argument");
+    const int n = init_points, D = c->t.D, deg = 3;
+    if (sample_count < 1) return sspp::set_error(SSPP_E_INVAL, "sample_count must be >= 1");
+    if (n < deg + 1) return sspp::set_error(SSPP_E_INVAL, "init_points must be >= 4 for a cubic spline");
+    if (check_points < 2) return sspp::set_error(SSPP_E_INVAL, "check_points must be >= 2");
+    // initializePath (include/sspp.h:82-97): linear via points at t_i = i / (n - 1)
+    std::vector<double> u((size_t)n), pts((size_t)n * D), ctrl0((size_t)n * D);
+    for (int i = 0; i < n; ++i) {
+        const double t = (double)i / (n - 1);
+        u[i] = t;
+        for (int d = 0; d < D; ++d) pts[(size_t)i * D + d] = (1 - t) * start[d] + t * end[d];
+    }
+    if (sspp::interpolate(pts.data(), n, D, deg, u.data(), knots_out, ctrl0.data()) != 0)
+        return sspp::set_error(SSPP_E_INVAL, "initializePath: interpolation failed");
+    hipStream_t st = (hipStream_t)sspp::shared_stream(0);
+    const int64_t B = sample_count;
+    const size_t nc = (size_t)B * n * D;
+    Dev<double> d_ctrl, d_arc;
+    Dev<uint8_t> d_f;
+    Dev<sspp_best> d_b;
+    int rc;
+    if ((rc = d_ctrl.reserve(nc)) || (rc = d_arc.reserve((size_t)B)) || (rc = d_f.reserve((size_t)B)) ||
+        (rc = d_b.reserve(1)))
+        return rc;
+    rc = sspp_chain_sample_score(c, knots_out, deg, ctrl0.data(), n, check_points, sigma, limits, seed, 0, B, d_arc.p,
+                                 d_f.p, d_ctrl.p, d_b.p, st);
+    if (!rc && ctrl_out) rc = hip_fail(hipMemcpyAsync(ctrl_out, d_ctrl.p, sizeof(double) * nc, hipMemcpyDeviceToHost, st), "copy candidates");
+    return chain_read_back(st, rc, B, d_arc, d_f, d_b, arc_out, feasible_out, best_out);
+}

@@ -99,6 +99,13 @@ int sspp_scene_create(const sspp_model* m, int mode, int arg, int count_static, 
     sspp::clear_error();
     if (!m || !out) return sspp::set_error(SSPP_E_INVAL, "sspp_scene_create: null argument");
     const int nb = m->nbody();
+    // a scene's movers are free bodies; an articulated model goes to sspp_chain_create
+    if (const int js = m->first_scalar_joint(); js >= 0)
+        return sspp::set_error(SSPP_E_UNSUPPORTED,
+                               "sspp_scene_create: joint '" + m->jnt_names[js] + "' (joint " + std::to_string(js) +
+                                   ", " + (m->jnt_type[js] == 2 ? "slide" : "hinge") + ") on body '" +
+                                   m->body_names[m->jnt_body[js]] +
+                                   "': scenes take free bodies only; bind an articulated model with sspp_chain_create");
     std::vector<int> mover_bodies;
     if (mode == SSPP_MODE_QPOS) {
         if (arg < 1 || arg > 16) return sspp::set_error(SSPP_E_INVAL, "dof must be in [1, 16]");

@@ -8,6 +8,10 @@
 //   Spline{3,6,7,9}()  .ctrls() -> (N, n_ctrl) float64 view
 //   create_model_capsule(uint64), create_data_capsule(uint64)
 // Beyond the reference: .plan_many(starts, ends, ...) — many plan() queries in one launch.
+// An XML with hinge / slide joints (an arm) plans through a chain (sspp_chain_*): plan, checkCollision,
+// computeArcLength, findBestPath, evaluate, initializePath, sampleWithNoise and get_ctrl_pts work as
+// for free bodies; plan_many, set_qpos / set_body_pose / get_qpos and contact_report raise
+// RuntimeError (SSPP_E_UNSUPPORTED) for it.
 // Everything planner-side goes through the C ABI (include/sspp_hip.h) into the HIP kernels;
 // this file holds no numerics beyond argument marshalling.
 //
@@ -89,10 +93,66 @@ class Planner {
 public:
     explicit Planner(const std::string& xml) : xml_path_(xml) {
         sspp_model* m = nullptr;
-        int rc = sspp_model_load_mjcf(xml.c_str(), &m);
+        // the joint-accepting loader: a model of free and jointless bodies is the same model either
+        // way and takes the scene / planner objects below; one with a hinge or a slide joint takes a
+        // chain (sspp_chain_*, DESIGN.md §5 "Articulated movers")
+        int rc = sspp_model_load_mjcf_joints(xml.c_str(), &m);
         if (rc < 0)
             throw std::runtime_error(std::string("Failed to load MuJoCo model from XML: ") + sspp_last_error());
         model_.reset(m);
+        sspp_joint_view jv{};
+        ck(sspp_model_joints_get(m, &jv), "joints");
+        for (int j = 0; j < jv.njnt; ++j) articulated_ = articulated_ || jv.jnt_type[j] != SSPP_JNT_FREE;
+    }
+
+    // plan() of an articulated model: the same candidates, scored through the chain
+    py::tuple plan_chain(const std::vector<double>& a, const std::vector<double>& b, double sigma,
+                         const std::vector<double>& l, int sample_count, int check_points, int init_points) {
+        auto lk = lock();
+        ensure_chain();
+        const int n = init_points;
+        const size_t nd = (size_t)n * N;
+        std::vector<double> knots((size_t)n + 4), ctrl((size_t)sample_count * nd), arc((size_t)sample_count);
+        std::vector<uint8_t> feas((size_t)sample_count);
+        sspp_best best{};
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = sspp_chain_plan_host(chain_.get(), a.data(), b.data(), sigma, l.data(), sample_count, check_points,
+                                      init_points, seed, knots.data(), ctrl.data(), feas.data(), arc.data(), &best);
+        }
+        ck(rc, "plan");
+        py::list paths;
+        last_feasible_ids.clear();
+        for (int k = 0; k < sample_count; ++k) {
+            if (!feas[(size_t)k]) continue;
+            Spline<N> s;
+            s.set_from_nd(knots.data(), (int)knots.size(), ctrl.data() + (size_t)k * nd, n);
+            if (k == best.index) path_ = s;
+            paths.append(py::cast(std::move(s)));
+            last_feasible_ids.push_back(k);
+        }
+        std::cout << "Sampled " << sample_count << " splines. Successful paths found: " << best.count << std::endl;
+        last_best_cost = best.cost;
+        last_best_index = best.index;
+        return py::make_tuple(best.index >= 0, paths);
+    }
+
+    // one call for checkCollision / computeArcLength / findBestPath of an articulated model
+    void score_chain(const double* knots, const double* ctrl, int64_t B, int n, int W, int with_collision, double* arc,
+                     uint8_t* feas, sspp_best* best, const char* what) {
+        ensure_chain();
+        int rc;
+        {
+            py::gil_scoped_release nogil;
+            rc = sspp_chain_score_ctrl_host(chain_.get(), knots, 3, ctrl, B, n, W, with_collision, arc, feas, best);
+        }
+        ck(rc, what);
+    }
+
+    [[noreturn]] void no_chain(const char* what) const {
+        throw std::runtime_error(std::string(what) + ": SSPP_E_UNSUPPORTED (-5): unsupported for an articulated model "
+                                 "(one with hinge or slide joints)");
     }
 
     bool initializePath(py::array_t<double, py::array::forcecast> start,
@@ -123,6 +183,7 @@ public:
         if (sample_count < 1) throw py::value_error("sample_count must be >= 1");
         if (init_points < 4) throw py::value_error("init_points must be >= 4");
         if (check_points < 2) throw py::value_error("check_points must be >= 2");
+        if (articulated_) return plan_chain(a, b, sigma, l, sample_count, check_points, init_points);
         auto lk = lock();  // held until the shared buffers below have been read
         ensure_planner();
         const int n = init_points;
@@ -174,6 +235,7 @@ public:
                        py::array_t<double, py::array::c_style | py::array::forcecast> ends, double sigma,
                        py::array_t<double, py::array::forcecast> limits, int sample_count, int check_points,
                        int init_points, py::object seeds) {
+        if (articulated_) no_chain("plan_many");
         if (starts.ndim() != 2 || starts.shape(1) != N)
             throw py::value_error("starts: expected shape (Q, " + std::to_string(N) + ")");
         if (ends.ndim() != 2 || ends.shape(1) != N)
@@ -250,11 +312,15 @@ public:
         if (num_samples < 1) throw py::value_error("num_samples must be >= 1");
         if (s.ctrl.empty()) throw py::value_error("checkCollision on an empty spline");
         auto lk = lock();
-        ensure_planner();
         double arc;
         uint8_t feas;
         sspp_best best;
         std::vector<double> c = s.ctrl_nd();
+        if (articulated_) {
+            score_chain(s.knots.data(), c.data(), 1, s.n(), num_samples, 1, &arc, &feas, &best, "checkCollision");
+            return feas == 0;
+        }
+        ensure_planner();
         int rc;
         {
             py::gil_scoped_release nogil;
@@ -273,6 +339,7 @@ public:
     py::list contact_report(const Spline<N>& s, int num_samples) {
         if (num_samples < 1) throw py::value_error("num_samples must be >= 1");
         if (s.ctrl.empty()) throw py::value_error("contact_report on an empty spline");
+        if (articulated_) no_chain("contact_report");
         auto lk = lock();
         ensure_scene();
         int np = 0, ns = 0;
@@ -308,11 +375,15 @@ public:
         if (check_points < 2) throw py::value_error("check_points must be >= 2");
         if (s.ctrl.empty()) throw py::value_error("computeArcLength on an empty spline");
         auto lk = lock();
-        ensure_planner();
         double arc;
         uint8_t feas;
         sspp_best best;
         std::vector<double> c = s.ctrl_nd();
+        if (articulated_) {
+            score_chain(s.knots.data(), c.data(), 1, s.n(), check_points, 0, &arc, &feas, &best, "computeArcLength");
+            return arc;
+        }
+        ensure_planner();
         ck(sspp_planner_score(planner_.get(), s.knots.data(), 3, c.data(), 1, s.n(), check_points, 0,
                               &arc, &feas, &best), "computeArcLength");
         return arc;
@@ -334,10 +405,15 @@ public:
             std::vector<uint8_t> feas(paths.size());
             sspp_best b;
             auto lk = lock();
-            ensure_planner();
-            ck(sspp_planner_score(planner_.get(), f.knots.data(), 3, all.data(), (int64_t)paths.size(),
-                                  f.n(), check_points, 0, arc.data(), feas.data(), &b),
-               "findBestPath");
+            if (articulated_) {
+                score_chain(f.knots.data(), all.data(), (int64_t)paths.size(), f.n(), check_points, 0, arc.data(),
+                            feas.data(), &b, "findBestPath");
+            } else {
+                ensure_planner();
+                ck(sspp_planner_score(planner_.get(), f.knots.data(), 3, all.data(), (int64_t)paths.size(),
+                                      f.n(), check_points, 0, arc.data(), feas.data(), &b),
+                   "findBestPath");
+            }
             best = b.cost; bi = b.index;
         } else {
             for (size_t i = 0; i < paths.size(); ++i) {
@@ -362,6 +438,7 @@ public:
     // last_feasible_ids) is left as it was.
     void set_qpos(py::array_t<double, py::array::forcecast> qpos) {
         py::array_t<double> c = py::array_t<double, py::array::c_style | py::array::forcecast>::ensure(qpos);
+        if (articulated_) no_chain("set_qpos");
         auto lk = lock();
         ensure_scene();
         ck(sspp_scene_set_qpos(scene_.get(), c.data(), (int)c.size()), "set_qpos");
@@ -369,6 +446,7 @@ public:
     void set_body_pose(const std::string& name, py::array_t<double, py::array::forcecast> pos,
                        py::array_t<double, py::array::forcecast> quat) {
         auto p = vec_of(pos, 3, "pos"), q = vec_of(quat, 4, "quat");
+        if (articulated_) no_chain("set_body_pose");
         const int body = sspp_model_body_id(model_.get(), name.c_str());
         ck(body, "set_body_pose");
         auto lk = lock();
@@ -376,6 +454,7 @@ public:
         ck(sspp_scene_set_body_pose(scene_.get(), body, p.data(), q.data()), "set_body_pose");
     }
     py::array_t<double> get_qpos() {
+        if (articulated_) no_chain("get_qpos");
         auto lk = lock();
         ensure_scene();
         sspp_model_view v{};
@@ -386,6 +465,7 @@ public:
     }
     // diagnostics: a read-back option (SSPP_OPT_*) of the last plan() shape's job
     int64_t option(int key) {
+        if (articulated_) no_chain("_option");
         auto lk = lock();
         ensure_planner();
         int64_t v = 0;
@@ -402,6 +482,7 @@ private:
     struct ModelDel { void operator()(sspp_model* m) const { sspp_model_free(m); } };
     struct SceneDel { void operator()(sspp_scene* s) const { sspp_scene_free(s); } };
     struct PlannerDel { void operator()(sspp_planner* p) const { sspp_planner_free(p); } };
+    struct ChainDel { void operator()(sspp_chain* c) const { sspp_chain_free(c); } };
 
     // One call at a time per object: plan / checkCollision / computeArcLength / findBestPath
     // share the sspp_planner's device and pinned buffers and this object's host buffers.  The
@@ -421,6 +502,13 @@ private:
         // Q7), static-static contacts included
         ck(sspp_scene_create(model_.get(), SSPP_MODE_QPOS, N, 1, &s), "scene");
         scene_.reset(s);
+    }
+
+    void ensure_chain() {
+        if (chain_) return;
+        sspp_chain* c = nullptr;
+        ck(sspp_chain_create(model_.get(), N, 1, &c), "chain");  // (count_static = 1, as ensure_scene)
+        chain_.reset(c);
     }
 
     void ensure_planner() {
@@ -457,6 +545,8 @@ private:
     std::unique_ptr<sspp_model, ModelDel> model_;
     std::unique_ptr<sspp_scene, SceneDel> scene_;
     std::unique_ptr<sspp_planner, PlannerDel> planner_;  // declared after scene_: freed first
+    bool articulated_ = false;                            // the model has a hinge or a slide joint
+    std::unique_ptr<sspp_chain, ChainDel> chain_;         // its chain (scene_ / planner_ stay empty)
     std::vector<double> knots_buf_, arc_buf_, ctrl_buf_;
     std::vector<int64_t> ids_buf_;
     Spline<N> path_;

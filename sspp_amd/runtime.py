@@ -103,11 +103,34 @@ def reduce_best_device(parts, out, stream=None):
 class Model:
     """Parsed MJCF scene (SamplingPathPlanner(xml_path) semantics: the string is a path)."""
 
-    def __init__(self, xml_path):
+    def __init__(self, xml_path, joints=False):
+        """joints=True also accepts hinge and slide joints (sspp_model_load_mjcf_joints): such a
+        model binds to a Chain, not to a Scene."""
         h = C.c_void_p()
-        check(lib().sspp_model_load_mjcf(str(xml_path).encode(), C.byref(h)), "load MJCF")
+        load = lib().sspp_model_load_mjcf_joints if joints else lib().sspp_model_load_mjcf
+        check(load(str(xml_path).encode(), C.byref(h)), "load MJCF")
         self._h = h
         self.path = str(xml_path)
+
+    def joints(self):
+        """The joints in body pre-order (document order within a body): type (0 free, 2 slide,
+        3 hinge), body, qpos address, unit axis and pos in the body frame, names, and qpos0 (a
+        hinge's / slide's reference value at its address)."""
+        v = _lib.JointView()
+        check(lib().sspp_model_joints_get(self._h, C.byref(v)), "model joints")
+        nj, nq = v.njnt, v.nq
+
+        def arr(p, n, dt, shape):
+            if n == 0:
+                return np.zeros(shape, dt)
+            return np.ctypeslib.as_array(p, shape=(n,)).astype(dt).reshape(shape)
+
+        return dict(
+            jnt_type=arr(v.jnt_type, nj, np.int32, (nj,)), jnt_body=arr(v.jnt_body, nj, np.int32, (nj,)),
+            jnt_qpos_adr=arr(v.jnt_qpos_adr, nj, np.int32, (nj,)), jnt_axis=arr(v.jnt_axis, 3 * nj, np.float64, (nj, 3)),
+            jnt_pos=arr(v.jnt_pos, 3 * nj, np.float64, (nj, 3)), qpos0=arr(v.qpos0, nq, np.float64, (nq,)),
+            jnt_names=[(lib().sspp_model_joint_name(self._h, j) or b"").decode() for j in range(nj)],
+        )
 
     @property
     def handle(self):
@@ -279,6 +302,98 @@ class Scene:
         if getattr(self, "_h", None) and _lib._lib is not None:
             _lib._lib.sspp_scene_free(self._h)
             self._h = None
+
+
+class Chain:
+    """An articulated model (Model(path, joints=True)) bound to SamplingPathPlanner's pose rule
+    q[0:dof] -> qpos[0:dof]: forward kinematics of its driven bodies, contact decisions and spline
+    scoring on the device (sspp_chain_*, DESIGN.md §5 "Articulated movers").  count_static: a
+    contact among the static geoms makes every pose / candidate infeasible, as for a Scene."""
+
+    def __init__(self, model, dof, count_static=True):
+        h = C.c_void_p()
+        check(lib().sspp_chain_create(model.handle, int(dof), int(bool(count_static)), C.byref(h)), "chain create")
+        self._h = h
+        self.model = model  # keep alive
+        self.dof = int(dof)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib._lib is not None:
+            _lib._lib.sspp_chain_free(self._h)
+            self._h = None
+
+    def info(self):
+        i = _lib.ChainInfo()
+        check(lib().sspp_chain_get_info(self._h, C.byref(i)), "chain info")
+        return {k: getattr(i, k) for k, _ in _lib.ChainInfo._fields_}
+
+    def pairs(self):
+        """The pair table in evaluation order: dicts of geom ids, names, types, moving flags, margin."""
+        n = C.c_int()
+        check(lib().sspp_chain_pairs(self._h, None, 0, C.byref(n)), "chain pairs")
+        infos = (PairInfo * max(n.value, 1))()
+        check(lib().sspp_chain_pairs(self._h, infos, n.value, C.byref(n)), "chain pairs")
+        gt = self.model.arrays()["geom_type"]
+        return [dict(geom1=int(p.geom1), geom2=int(p.geom2), name1=self.model.geom_name(p.geom1),
+                     name2=self.model.geom_name(p.geom2), type1=int(gt[p.geom1]), type2=int(gt[p.geom2]),
+                     moving1=bool(p.moving1), moving2=bool(p.moving2), margin=float(p.margin))
+                for p in infos[:n.value]]
+
+    def _poses(self, q):
+        torch = _torch()
+        if not (hasattr(q, "is_cuda") and q.is_cuda):
+            q = torch.as_tensor(np.array(q, dtype=np.float64), device="cuda")
+        q = q.to(torch.float64).contiguous()
+        if q.ndim != 2 or q.shape[1] != self.dof:
+            raise SsppError("chain failed (-1): poses must be [N, %d], got %s" % (self.dof, tuple(q.shape)))
+        return q
+
+    def fk(self, q, stream=None):
+        """World poses of every geom at N poses q [N, dof]: (gpos [N, ngeom, 3], gmat [N, ngeom, 9])
+        float64 CUDA tensors.  Synchronises on its stream."""
+        torch = _torch()
+        q = self._poses(q)
+        N, ng = int(q.shape[0]), self.info()["n_geoms"]
+        gpos = torch.empty((N, ng, 3), dtype=torch.float64, device=q.device)
+        gmat = torch.empty((N, ng, 9), dtype=torch.float64, device=q.device)
+        check(lib().sspp_chain_fk(self._h, _ptr(q), N, _ptr(gpos), _ptr(gmat), _stream(stream)), "chain fk")
+        _sync(stream)
+        return gpos, gmat
+
+    def contacts(self, q, stream=None):
+        """One byte per pose of q [N, dof]: 1 in contact.  A uint8 CUDA tensor [N]; synchronises."""
+        torch = _torch()
+        q = self._poses(q)
+        N = int(q.shape[0])
+        hit = torch.empty((N,), dtype=torch.uint8, device=q.device)
+        check(lib().sspp_chain_contacts(self._h, _ptr(q), N, _ptr(hit), _stream(stream)), "chain contacts")
+        _sync(stream)
+        return hit
+
+    def score_ctrl(self, knots, degree, ctrl, check_points, first_id, arc, feasible, best, stream=None):
+        """checkCollision + computeArcLength + findBestPath on the splines ctrl [B, n, dof] (a CUDA
+        tensor) into the caller's device buffers (SsppJob.score_ctrl's contract).  Asynchronous."""
+        knots = _f64(knots)
+        B, n = int(ctrl.shape[0]), int(ctrl.shape[1])
+        check(lib().sspp_chain_score_ctrl(self._h, _dptr(knots), int(degree), _ptr(ctrl), int(first_id), B, n,
+                                          int(check_points), _ptr(arc), _ptr(feasible), _ptr(best), _stream(stream)),
+              "chain score_ctrl")
+
+    def sample_score(self, knots, degree, init_ctrl, sigma, limits, check_points, first_id, B, arc, feasible, best,
+                     ctrl_out=None, seed=DEFAULT_SEED, stream=None):
+        """The same on sampleWithNoise's candidates for (seed, ids first_id .. first_id + B)."""
+        knots = _f64(knots)
+        init = np.ascontiguousarray(np.asarray(init_ctrl, dtype=np.float64))
+        n = int(init.shape[0])
+        lim = _f64(limits, self.dof)
+        check(lib().sspp_chain_sample_score(self._h, _dptr(knots), int(degree), _dptr(init), n, int(check_points),
+                                            float(sigma), _dptr(lim), int(seed), int(first_id), int(B), _ptr(arc),
+                                            _ptr(feasible), _ptr(ctrl_out), _ptr(best), _stream(stream)),
+              "chain sample_score")
 
 
 def interpolate(pts, degree, u):
