@@ -60,9 +60,11 @@ $(OBJDIR)/stamp.o: $(SRCS) sspp_amd/_stamp.py
 	g++ $(HOSTFLAGS) -c $(OBJDIR)/stamp.cpp -o $@
 
 # the contact report's kernels (sspp_scene_contacts, sspp_job_path_contacts) and the articulated
-# movers' (sspp_chain_*): units of their own; sspp_chain.h is read by sspp_chain.hip alone
-$(OBJDIR)/sspp_chain.o: $(SRC)/sspp_chain.h
-$(LIB): $(OBJDIR)/sspp_kernels.o $(INST) $(OBJDIR)/sspp_report.o $(OBJDIR)/sspp_chain.o $(OBJDIR)/ces.o $(OBJDIR)/planner.o $(OBJDIR)/sspp_capi.o $(OBJDIR)/mjcf.o $(OBJDIR)/spline_host.o $(OBJDIR)/sspp_hostapi.o $(OBJDIR)/stamp.o
+# movers' (sspp_chain_*) with their own contact report: units of their own; the chain's headers are
+# read by those two units alone
+$(OBJDIR)/sspp_chain.o: $(SRC)/sspp_chain.h $(SRC)/sspp_chain_dev.h
+$(OBJDIR)/sspp_chain_report.o: $(SRC)/sspp_chain.h $(SRC)/sspp_chain_dev.h $(SRC)/sspp_chain_report.h
+$(LIB): $(OBJDIR)/sspp_kernels.o $(INST) $(OBJDIR)/sspp_report.o $(OBJDIR)/sspp_chain.o $(OBJDIR)/sspp_chain_report.o $(OBJDIR)/ces.o $(OBJDIR)/planner.o $(OBJDIR)/sspp_capi.o $(OBJDIR)/mjcf.o $(OBJDIR)/spline_host.o $(OBJDIR)/sspp_hostapi.o $(OBJDIR)/stamp.o
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 

@@ -50,6 +50,9 @@
  *   sspp_chain_create / _fk / _contacts <- mj_forward on such a model (mj_kinematics + collision)
  *   sspp_chain_score_ctrl / _sample_score <- checkCollision + computeArcLength + findBestPath
  *                               (include/sspp.h:132-192) / plan's candidate loop (203-219) for it
+ *   sspp_chain_pair_contacts / _path_contacts / _first_contacts / _static_pairs
+ *                            <- reading mjData::contact[] after mj_forward on such a model, per
+ *                               pose, per waypoint of a spline, and up to a spline's first contact
  *
  * Device pointers: every `d_` argument is device memory (hipMalloc / torch.cuda); the job
  * run functions issue only asynchronous work on `stream` (hipStream_t passed as void*; NULL =
@@ -332,7 +335,7 @@ int sspp_path_contacts_host(const sspp_scene* s, const double* knots, int degree
  * The device calls are asynchronous on `stream`; N = 0 or B = 0 is SSPP_OK without a launch.  The
  * scoring calls keep a scene-less job per spline shape (knots, n, W): the first call of a shape or
  * of a larger B allocates, later ones do not.  Out of scope for a chain: TaskSpacePlanner / CES,
- * plan_many, re-posing, the per-pair contact report, joint limits. */
+ * plan_many, re-posing, joint limits. */
 #define SSPP_JNT_FREE 0
 #define SSPP_JNT_SLIDE 2
 #define SSPP_JNT_HINGE 3
@@ -391,6 +394,59 @@ int sspp_chain_plan_host(sspp_chain* c, const double* start, const double* end, 
                          int sample_count, int check_points, int init_points, uint64_t seed, double* knots_out,
                          double* ctrl_out /* [sample_count][init_points][dof] */, uint8_t* feasible_out,
                          double* arc_out, sspp_best* best_out);
+
+/* ---- contact report for arms (DESIGN.md §5 "Contact report for arms") ----
+ * Which pairs of a chain a pose or a path touches.  Columns: the chain's pair table in
+ * sspp_chain_pairs order, P = n_pairs.  Per pose and pair, the test sspp_chain_contacts runs, but for
+ * every pair (nothing is skipped after a hit): the geoms' world poses, the bounding-sphere cull (a
+ * pair with a zero bounding radius, a plane's, is never culled; a culled pair reports 0 / 0), then
+ * `contact` = the collider's contact count (dist <= margin) and, when asked for, `deep` = its count
+ * of contacts with dist < -1e-3, geom 1 first by (type, model index).  The counts mean what the
+ * free-body report's mean (DESIGN.md §4 "What the contact report counts"): true counts for the
+ * primitive colliders, 0 / 1 for box-box, cylinder-box and cylinder-cylinder, box-box `deep` = the
+ * manifold's deep points (deep > contact is normal there).  Outputs are dense uint8_t, every entry
+ * written, zeros included.  Static-static pairs are not columns, and count_static does not change
+ * the report; sspp_chain_static_pairs lists them, (geom1, geom2) order, with their counts at the
+ * chain's static poses (out / contact / deep may be NULL to read *n only; cap < n is SSPP_E_INVAL);
+ * their `contact` counts sum to sspp_chain_info::static_contacts.
+ *   sspp_chain_pair_contacts   N poses -> [N][P] counts; d_deep may be NULL
+ *   sspp_chain_path_contacts   B caller splines sharing one knot vector (degree 2 or 3) ->
+ *                              [B][W + 1][P] counts; waypoint i at u = i / W, i = 0..W
+ *                              (checkCollision's grid), evaluated as sspp_chain_score_ctrl's
+ *                              feasibility kernel evaluates it (the scene-less job's basis rows,
+ *                              eval_pt's products and fma order): its poses bit for bit
+ *   sspp_chain_first_contacts  per path {waypoint, pair}: the lowest waypoint with any contact and
+ *                              the lowest column in contact there; {-1, -1} for a path that touches
+ *                              nothing.  Static contacts are not counted: on a chain created with
+ *                              count_static = 0, waypoint == -1 exactly where sspp_chain_score_ctrl
+ *                              says feasible.  8 bytes per path, and a path stops at its first
+ *                              contact, where the dense form is (W + 1) P bytes per path and count
+ * The device calls are asynchronous on `stream` and do not synchronise.  N, B or P = 0 is SSPP_OK
+ * without a launch (sspp_chain_first_contacts with P = 0 fills its records with -1); a NULL input or
+ * d_contact (d_first) with something to write is SSPP_E_INVAL; n < 1, W < 1 or more than 2^31 - 1
+ * workgroups (one per 64 poses or waypoints; one per path for first_contacts) is SSPP_E_INVAL.  The
+ * path forms take the scene-less job of the spline shape from the chain's cache (the first call of a
+ * shape allocates and is synchronous, later ones are not) and read its basis rows only: they run no
+ * scoring launch. */
+typedef struct sspp_chain_first {
+    int32_t waypoint; /* lowest waypoint in contact, -1: none */
+    int32_t pair;     /* lowest column in contact at that waypoint, -1: none */
+} sspp_chain_first;
+int sspp_chain_static_pairs(const sspp_chain* c, sspp_pair_info* out, uint8_t* contact, uint8_t* deep, int cap, int* n);
+int sspp_chain_pair_contacts(const sspp_chain* c, const double* d_q /* [N][dof] */, int64_t N,
+                             uint8_t* d_contact /* [N][P] */, uint8_t* d_deep /* [N][P], nullable */, void* stream);
+int sspp_chain_path_contacts(sspp_chain* c, const double* knots /* host [n + degree + 1] */, int degree,
+                             const double* d_ctrl /* [B][n][dof] */, int64_t B, int n, int W,
+                             uint8_t* d_contact /* [B][W + 1][P] */, uint8_t* d_deep /* nullable */, void* stream);
+int sspp_chain_first_contacts(sspp_chain* c, const double* knots, int degree, const double* d_ctrl /* [B][n][dof] */,
+                              int64_t B, int n, int W, sspp_chain_first* d_first /* [B] */, void* stream);
+/* The same on host buffers, host-synchronous: they run on the drop-in planners' shared stream and
+ * wait for that stream only. */
+int sspp_chain_pair_contacts_host(const sspp_chain* c, const double* q, int64_t N, uint8_t* contact, uint8_t* deep);
+int sspp_chain_path_contacts_host(sspp_chain* c, const double* knots, int degree, const double* ctrl /* [B][n][dof] */,
+                                  int64_t B, int n, int W, uint8_t* contact /* [B][W + 1][P] */, uint8_t* deep);
+int sspp_chain_first_contacts_host(sspp_chain* c, const double* knots, int degree, const double* ctrl, int64_t B, int n,
+                                   int W, sspp_chain_first* first /* [B] */);
 
 /* ---- splines (host) ---- */
 int sspp_interpolate(const double* pts /* [n][D] */, int n, int D, int degree,

@@ -69,6 +69,10 @@ class ChainInfo(C.Structure):
 CHAIN_MAX_BODIES, CHAIN_MAX_DOF, CHAIN_MAX_PAIRS = 16, 16, 512
 
 
+class ChainFirst(C.Structure):
+    _fields_ = [("waypoint", C.c_int32), ("pair", C.c_int32)]
+
+
 class SsppArgs(C.Structure):
     _fields_ = [("knots", C.POINTER(C.c_double)), ("degree", C.c_int),
                 ("init_ctrl", C.POINTER(C.c_double)), ("n_ctrl", C.c_int), ("dof", C.c_int),
@@ -159,6 +163,15 @@ SIGNATURES = {
                                              C.POINTER(Best)]),
     "sspp_chain_plan_host": (C.c_int, [_vp, _d, _d, C.c_double, _d, _i, _i, _i, C.c_uint64, _d, _d,
                                        C.POINTER(C.c_uint8), _d, C.POINTER(Best)]),
+    "sspp_chain_static_pairs": (C.c_int, [_vp, C.POINTER(PairInfo), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _i,
+                                          C.POINTER(C.c_int)]),
+    "sspp_chain_pair_contacts": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),
+    "sspp_chain_path_contacts": (C.c_int, [_vp, _d, _i, _vp, _i64, _i, _i, _vp, _vp, _vp]),
+    "sspp_chain_first_contacts": (C.c_int, [_vp, _d, _i, _vp, _i64, _i, _i, _vp, _vp]),
+    "sspp_chain_pair_contacts_host": (C.c_int, [_vp, _d, _i64, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "sspp_chain_path_contacts_host": (C.c_int, [_vp, _d, _i, _d, _i64, _i, _i, C.POINTER(C.c_uint8),
+                                                C.POINTER(C.c_uint8)]),
+    "sspp_chain_first_contacts_host": (C.c_int, [_vp, _d, _i, _d, _i64, _i, _i, C.POINTER(ChainFirst)]),
     "sspp_interpolate": (C.c_int, [_d, _i, _i, _i, _d, _d, _d]),
     "sspp_spline_eval": (C.c_int, [_d, _i, _i, _d, _i, C.c_double, _d]),
     "sspp_job_create_sspp": (C.c_int, [_vp, C.POINTER(SsppArgs), _i64, C.POINTER(_vp)]),

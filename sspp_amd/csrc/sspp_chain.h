@@ -233,12 +233,37 @@ SSPP_HD int chain_contact(GP geoms, PP pairs, int np, const FR& fr) {
 }
 
 // ---------------------------------------------------------------- host: the tables of (model, D)
+// a static-static pair, (geom1, geom2) order, with its counts at the static poses (the contact
+// report's sspp_chain_static_pairs; the contact counts sum to static_contacts)
+struct CStatic {
+    int32_t g1, g2;
+    double margin;
+    uint8_t contact, deep;
+};
+
+// counts of one pair at world poses: the bounding-sphere cull (a zero rbound is never culled), then
+// collide<false>'s count and collide<true>'s deep count in the generic form, geom F first.  The one
+// test behind static_contacts and the static pairs' report.
+inline void chain_static_counts(const CGeom& F, const CGeom& S, double margin, int* contact, int* deep) {
+    *contact = *deep = 0;
+    if (F.rbound > 0.0 && S.rbound > 0.0) {
+        const double dc[3] = {S.wpos[0] - F.wpos[0], S.wpos[1] - F.wpos[1], S.wpos[2] - F.wpos[2]};
+        const double thr = F.rbound + S.rbound + margin;
+        if (dot3(dc, dc) > thr * thr) return;
+    }
+    int unused = 0;
+    *contact = sspr::collide_form<false, sspr::kGeneric>(F.type, F.wpos, F.wmat, F.size, S.type, S.wpos, S.wmat, S.size,
+                                                         margin, &unused);
+    sspr::collide_form<true, sspr::kGeneric>(F.type, F.wpos, F.wmat, F.size, S.type, S.wpos, S.wmat, S.size, margin, deep);
+}
+
 struct ChainTables {
     int D = 0;
     std::vector<CBody> bodies;    // the driven bodies
     std::vector<CJoint> joints;   // their hinge / slide joints
     std::vector<CGeom> geoms;     // every geom
     std::vector<CPair> pairs;     // evaluated per pose, (geom1, geom2) order
+    std::vector<CStatic> statics; // static-static pairs, (geom1, geom2) order, evaluated once
     std::vector<int> slot_body;   // model body of a slot
     int n_moving_geoms = 0, n_static_geoms = 0, n_static_pairs = 0, static_contacts = 0;
 };
@@ -380,16 +405,10 @@ inline int chain_build(const sspp_model& m, int D, ChainTables& out) {
             // static-static: constant over poses, evaluated once (the per-pose test, its contact count
             // summed as sspb::scene_build sums static_contacts)
             out.n_static_pairs++;
-            const CGeom& F = out.geoms[P.a];
-            const CGeom& S = out.geoms[P.b];
-            if (F.rbound > 0.0 && S.rbound > 0.0) {
-                const double dc[3] = {S.wpos[0] - F.wpos[0], S.wpos[1] - F.wpos[1], S.wpos[2] - F.wpos[2]};
-                const double thr = F.rbound + S.rbound + P.margin;
-                if (dot3(dc, dc) > thr * thr) continue;
-            }
-            int unused = 0;
-            out.static_contacts += sspr::collide_form<false, sspr::kGeneric>(F.type, F.wpos, F.wmat, F.size, S.type, S.wpos,
-                                                                             S.wmat, S.size, P.margin, &unused);
+            int nc = 0, nd = 0;
+            chain_static_counts(out.geoms[P.a], out.geoms[P.b], P.margin, &nc, &nd);
+            out.static_contacts += nc;
+            out.statics.push_back(CStatic{g1, g2, P.margin, (uint8_t)nc, (uint8_t)nd});
         }
     }
     if ((int)out.pairs.size() > kMaxPairs)

@@ -16,30 +16,12 @@
 //   k_chain_best      findBestPath over the batch: lowest arc, lowest id on ties, the feasible count
 // Arc lengths and sampled candidates come from a scene-less SamplingPathPlanner job (k_sspp_c2f,
 // arc_all = 1): the existing code, bit for bit.
-#include "sspp_chain.h"
+#include "sspp_chain_dev.h"
 
 using namespace sspk;
 using namespace sspc;
 
 namespace sspc {
-
-constexpr int kChainBlock = 64;  // one wave: the frames' LDS is per lane, nothing is shared
-
-struct ChainT {
-    const CBody* __restrict__ bodies;
-    const CJoint* __restrict__ joints;
-    const CGeom* __restrict__ geoms;
-    const CPair* __restrict__ pairs;
-    int nd, ng, np, D;
-};
-
-struct LdsFrames {
-    double* base;  // + lane
-    __device__ __forceinline__ double get(int slot, int c) const { return base[(slot * 7 + c) * kChainBlock]; }
-    __device__ __forceinline__ void set(int slot, int c, double v) const { base[(slot * 7 + c) * kChainBlock] = v; }
-};
-
-inline size_t chain_lds(int nd) { return sizeof(double) * 7 * kChainBlock * (size_t)std::max(1, nd); }
 
 __global__ __launch_bounds__(kChainBlock) void k_chain_fk(const ChainT T, const double* __restrict__ d_q,
                                                            const long long N, double* __restrict__ gpos,
@@ -159,32 +141,6 @@ __global__ __launch_bounds__(kBestBlock) void k_chain_best(const double* __restr
 
 }  // namespace sspc
 
-struct sspp_chain {
-    ChainTables t;
-    int count_static = 0;
-    int device = 0;
-    Dev<CBody> d_bodies;
-    Dev<CJoint> d_joints;
-    Dev<CGeom> d_geoms;
-    Dev<CPair> d_pairs;
-    // the scene-less job of the last spline shape (arc lengths, sampled candidates), the candidates
-    // of a sample_score call without d_ctrl_out, and the job's own argmin record (not the chain's)
-    sspp_job* job = nullptr;
-    std::vector<double> job_knots;
-    int job_p = 0, job_n = 0, job_W = 0;
-    int64_t job_cap = 0;
-    Dev<double> d_ctrl;
-    Dev<sspp_best> d_jobbest;
-    ~sspp_chain() {
-        if (job) sspp_job_free(job);
-    }
-    int static_block() const { return (count_static && t.static_contacts > 0) ? 1 : 0; }
-    ChainT view() const {
-        return ChainT{d_bodies.p, d_joints.p, d_geoms.p, d_pairs.p, (int)t.bodies.size(), (int)t.geoms.size(),
-                      (int)t.pairs.size(), t.D};
-    }
-};
-
 extern "C" int sspp_chain_create(const sspp_model* m, int dof, int count_static, sspp_chain** out) {
     sspp::clear_error();
     if (!m || !out) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_create: null argument");
@@ -274,7 +230,7 @@ extern "C" int sspp_chain_contacts(const sspp_chain* c, const double* d_q, int64
 
 // the scene-less job for splines of this shape (created or replaced on a new shape or a larger
 // batch: synchronous; otherwise nothing is allocated)
-static int chain_job(sspp_chain* c, const double* knots, int degree, int n, int W, int64_t B) {
+int sspc::chain_job(sspp_chain* c, const double* knots, int degree, int n, int W, int64_t B) {
     const int D = c->t.D;
     if (!knots) return sspp::set_error(SSPP_E_INVAL, "sspp_chain: null knots");
     if (degree < 2 || degree > 3 || n < degree + 1)

@@ -1,0 +1,60 @@
+// sspp_chain_dev.h — what the chain's two translation units share (sspp_chain.hip: kinematics,
+// contact decisions, scoring; sspp_chain_report.hip: the contact report): the device view of the
+// tables, the LDS-backed frame accessor, the chain object and its per-shape job cache.
+#pragma once
+#include "sspp_chain.h"
+
+namespace sspc {
+
+constexpr int kChainBlock = 64;  // one wave: the frames' LDS is per lane, nothing is shared
+
+struct ChainT {
+    const CBody* __restrict__ bodies;
+    const CJoint* __restrict__ joints;
+    const CGeom* __restrict__ geoms;
+    const CPair* __restrict__ pairs;
+    int nd, ng, np, D;
+};
+
+struct LdsFrames {
+    double* base;  // + lane
+    __device__ __forceinline__ double get(int slot, int c) const { return base[(slot * 7 + c) * kChainBlock]; }
+    __device__ __forceinline__ void set(int slot, int c, double v) const { base[(slot * 7 + c) * kChainBlock] = v; }
+};
+
+inline size_t chain_lds(int nd) { return sizeof(double) * 7 * kChainBlock * (size_t)std::max(1, nd); }
+
+}  // namespace sspc
+
+struct sspp_chain {
+    sspc::ChainTables t;
+    int count_static = 0;
+    int device = 0;
+    sspo::Dev<sspc::CBody> d_bodies;
+    sspo::Dev<sspc::CJoint> d_joints;
+    sspo::Dev<sspc::CGeom> d_geoms;
+    sspo::Dev<sspc::CPair> d_pairs;
+    // the scene-less job of the last spline shape (arc lengths, sampled candidates, the report's
+    // basis rows), the candidates of a sample_score call without d_ctrl_out, and the job's own
+    // argmin record (not the chain's)
+    sspp_job* job = nullptr;
+    std::vector<double> job_knots;
+    int job_p = 0, job_n = 0, job_W = 0;
+    int64_t job_cap = 0;
+    sspo::Dev<double> d_ctrl;
+    sspo::Dev<sspp_best> d_jobbest;
+    ~sspp_chain() {
+        if (job) sspp_job_free(job);
+    }
+    int static_block() const { return (count_static && t.static_contacts > 0) ? 1 : 0; }
+    sspc::ChainT view() const {
+        return sspc::ChainT{d_bodies.p, d_joints.p, d_geoms.p, d_pairs.p, (int)t.bodies.size(), (int)t.geoms.size(),
+                            (int)t.pairs.size(), t.D};
+    }
+};
+
+namespace sspc {
+// the scene-less job for splines of this shape (created or replaced on a new shape or a larger
+// batch: synchronous; otherwise nothing is allocated).  Defined in sspp_chain.hip.
+int chain_job(sspp_chain* c, const double* knots, int degree, int n, int W, int64_t B);
+}  // namespace sspc

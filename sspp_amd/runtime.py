@@ -194,6 +194,21 @@ class Model:
         return out
 
 
+def _pair_dicts(model, infos, contact=None, deep=None):
+    """sspp_pair_info records as dicts (geom ids, names, types, moving flags, margin; with the counts
+    of a static-pairs call): Scene's and Chain's pair listings"""
+    gt = model.arrays()["geom_type"]
+    out = []
+    for k, p in enumerate(infos):
+        d = dict(geom1=int(p.geom1), geom2=int(p.geom2), name1=model.geom_name(p.geom1),
+                 name2=model.geom_name(p.geom2), type1=int(gt[p.geom1]), type2=int(gt[p.geom2]),
+                 moving1=bool(p.moving1), moving2=bool(p.moving2), margin=float(p.margin))
+        if contact is not None:
+            d["contact"], d["deep"] = int(contact[k]), int(deep[k])
+        out.append(d)
+    return out
+
+
 class Scene:
     """Model bound to its moving set, with device-resident geom/pair tables.  count_static: the
     SamplingPathPlanner feasibility counts the scene's static-static contacts too (the
@@ -250,25 +265,13 @@ class Scene:
 
     # Contact report (sspp_scene_pairs / _static_pairs / _contacts): which geom pairs a pose touches,
     # what the reference reads from mjData.contact[] (Collision::check_collision_point).
-    def _pair_dicts(self, infos, contact=None, deep=None):
-        gt = self.model.arrays()["geom_type"]
-        out = []
-        for k, p in enumerate(infos):
-            d = dict(geom1=int(p.geom1), geom2=int(p.geom2), name1=self.model.geom_name(p.geom1),
-                     name2=self.model.geom_name(p.geom2), type1=int(gt[p.geom1]), type2=int(gt[p.geom2]),
-                     moving1=bool(p.moving1), moving2=bool(p.moving2), margin=float(p.margin))
-            if contact is not None:
-                d["contact"], d["deep"] = int(contact[k]), int(deep[k])
-            out.append(d)
-        return out
-
     def pairs(self):
         """The moving pairs in report column order: a list of dicts (geom ids, names, types, margin)."""
         n = C.c_int()
         check(lib().sspp_scene_pairs(self._h, None, 0, C.byref(n)), "scene pairs")
         infos = (PairInfo * max(n.value, 1))()
         check(lib().sspp_scene_pairs(self._h, infos, n.value, C.byref(n)), "scene pairs")
-        return self._pair_dicts(infos[:n.value])
+        return _pair_dicts(self.model, infos[:n.value])
 
     def static_pairs(self):
         """The env-env pairs with their `contact` / `deep` counts at the scene's current poses."""
@@ -277,7 +280,7 @@ class Scene:
         infos = (PairInfo * max(n.value, 1))()
         c, d = (C.c_uint8 * max(n.value, 1))(), (C.c_uint8 * max(n.value, 1))()
         check(lib().sspp_scene_static_pairs(self._h, infos, c, d, n.value, C.byref(n)), "scene static pairs")
-        return self._pair_dicts(infos[:n.value], c, d)
+        return _pair_dicts(self.model, infos[:n.value], c, d)
 
     def contacts(self, q, deep=True, stream=None):
         """Per-pair contact counts of N poses: q [N, dof] (MODE_QPOS) or [N, 4] = (x, y, z, yaw)
@@ -337,11 +340,17 @@ class Chain:
         check(lib().sspp_chain_pairs(self._h, None, 0, C.byref(n)), "chain pairs")
         infos = (PairInfo * max(n.value, 1))()
         check(lib().sspp_chain_pairs(self._h, infos, n.value, C.byref(n)), "chain pairs")
-        gt = self.model.arrays()["geom_type"]
-        return [dict(geom1=int(p.geom1), geom2=int(p.geom2), name1=self.model.geom_name(p.geom1),
-                     name2=self.model.geom_name(p.geom2), type1=int(gt[p.geom1]), type2=int(gt[p.geom2]),
-                     moving1=bool(p.moving1), moving2=bool(p.moving2), margin=float(p.margin))
-                for p in infos[:n.value]]
+        return _pair_dicts(self.model, infos[:n.value])
+
+    def static_pairs(self):
+        """The static-static pairs with their `contact` / `deep` counts at the chain's static poses
+        (their contacts sum to info()["static_contacts"])."""
+        n = C.c_int()
+        check(lib().sspp_chain_static_pairs(self._h, None, None, None, 0, C.byref(n)), "chain static pairs")
+        infos = (PairInfo * max(n.value, 1))()
+        c, d = (C.c_uint8 * max(n.value, 1))(), (C.c_uint8 * max(n.value, 1))()
+        check(lib().sspp_chain_static_pairs(self._h, infos, c, d, n.value, C.byref(n)), "chain static pairs")
+        return _pair_dicts(self.model, infos[:n.value], c, d)
 
     def _poses(self, q):
         torch = _torch()
@@ -373,6 +382,60 @@ class Chain:
         check(lib().sspp_chain_contacts(self._h, _ptr(q), N, _ptr(hit), _stream(stream)), "chain contacts")
         _sync(stream)
         return hit
+
+    # Contact report (sspp_chain_pair_contacts / _path_contacts / _first_contacts): which pairs a pose
+    # or a path touches; columns in pairs() order, static-static pairs left to static_pairs().
+    def pair_contacts(self, q, deep=True, stream=None):
+        """Per-pair contact counts of N poses q [N, dof] (a CUDA tensor or an array).  Returns
+        (contact, deep): uint8 CUDA tensors [N, P] (deep is None with deep=False).  Synchronises on
+        its stream."""
+        torch = _torch()
+        q = self._poses(q)
+        N, P = int(q.shape[0]), self.info()["n_pairs"]
+        c = torch.empty((N, P), dtype=torch.uint8, device=q.device)
+        d = torch.empty((N, P), dtype=torch.uint8, device=q.device) if deep else None
+        check(lib().sspp_chain_pair_contacts(self._h, _ptr(q), N, _ptr(c), _ptr(d), _stream(stream)),
+              "chain pair_contacts")
+        _sync(stream)
+        return c, d
+
+    def _splines(self, ctrl):
+        torch = _torch()
+        if not (hasattr(ctrl, "is_cuda") and ctrl.is_cuda):
+            ctrl = torch.as_tensor(np.array(ctrl, dtype=np.float64), device="cuda")
+        ctrl = ctrl.to(torch.float64).contiguous()
+        if ctrl.ndim != 3 or ctrl.shape[2] != self.dof:
+            raise SsppError("chain failed (-1): splines must be [B, n, %d], got %s" % (self.dof, tuple(ctrl.shape)))
+        return ctrl
+
+    def path_contacts(self, knots, degree, ctrl, check_points, deep=True, stream=None):
+        """Per-pair contact counts of the splines ctrl [B, n, dof] at checkCollision's waypoints
+        u = i / check_points, i = 0..check_points (score_ctrl's poses bit for bit).  Returns
+        (contact, deep): uint8 CUDA tensors [B, check_points + 1, P].  Synchronises on its stream."""
+        torch = _torch()
+        knots = _f64(knots)
+        ctrl = self._splines(ctrl)
+        B, n, W, P = int(ctrl.shape[0]), int(ctrl.shape[1]), int(check_points), self.info()["n_pairs"]
+        c = torch.empty((B, W + 1, P), dtype=torch.uint8, device=ctrl.device)
+        d = torch.empty((B, W + 1, P), dtype=torch.uint8, device=ctrl.device) if deep else None
+        check(lib().sspp_chain_path_contacts(self._h, _dptr(knots), int(degree), _ptr(ctrl), B, n, W, _ptr(c), _ptr(d),
+                                             _stream(stream)), "chain path_contacts")
+        _sync(stream)
+        return c, d
+
+    def first_contacts(self, knots, degree, ctrl, check_points, stream=None):
+        """Per spline of ctrl [B, n, dof] its first contact: an int32 CUDA tensor [B, 2] of (lowest
+        waypoint in contact, lowest pairs() column in contact there), (-1, -1) for a spline that
+        touches nothing.  Static contacts are not counted.  Synchronises on its stream."""
+        torch = _torch()
+        knots = _f64(knots)
+        ctrl = self._splines(ctrl)
+        B, n = int(ctrl.shape[0]), int(ctrl.shape[1])
+        first = torch.empty((B, 2), dtype=torch.int32, device=ctrl.device)
+        check(lib().sspp_chain_first_contacts(self._h, _dptr(knots), int(degree), _ptr(ctrl), B, n, int(check_points),
+                                              _ptr(first), _stream(stream)), "chain first_contacts")
+        _sync(stream)
+        return first
 
     def score_ctrl(self, knots, degree, ctrl, check_points, first_id, arc, feasible, best, stream=None):
         """checkCollision + computeArcLength + findBestPath on the splines ctrl [B, n, dof] (a CUDA
