@@ -335,7 +335,7 @@ int sspp_path_contacts_host(const sspp_scene* s, const double* knots, int degree
  * The device calls are asynchronous on `stream`; N = 0 or B = 0 is SSPP_OK without a launch.  The
  * scoring calls keep a scene-less job per spline shape (knots, n, W): the first call of a shape or
  * of a larger B allocates, later ones do not.  Out of scope for a chain: TaskSpacePlanner / CES,
- * plan_many, re-posing, joint limits. */
+ * re-posing, joint limits. */
 #define SSPP_JNT_FREE 0
 #define SSPP_JNT_SLIDE 2
 #define SSPP_JNT_HINGE 3
@@ -394,6 +394,43 @@ int sspp_chain_plan_host(sspp_chain* c, const double* start, const double* end, 
                          int sample_count, int check_points, int init_points, uint64_t seed, double* knots_out,
                          double* ctrl_out /* [sample_count][init_points][dof] */, uint8_t* feasible_out,
                          double* arc_out, sspp_best* best_out);
+
+/* ---- query launches for arms (DESIGN.md §5 "Query launches for arms") ----
+ * sspp_chain_sample_score_queries scores 1 <= Q <= 64 queries of one arm and one spline shape in one
+ * launch sequence: the scene-less job's query launch (sspp_job_set_queries +
+ * sspp_job_sample_score_queries: candidates and arcs for all Q * B), one feasibility launch over the
+ * Q * B candidates, one argmin workgroup per query.  Row q of every output is, byte for byte, what
+ * sspp_chain_sample_score writes for query q alone (its init_ctrl, sigma, limits, seed, ids
+ * [first_id, first_id + B)): arcs (+inf over infeasible candidates), feasibility, the sampled control
+ * points, and the record (lowest arc, lowest id on ties, count = feasible candidates; index -1 and
+ * cost +inf without one; reserved 0).  d_best_ctrl[q] is the winner's control points, zeros without a
+ * winner; d_best and d_best_ctrl may be mapped pinned host memory.  Asynchronous on `stream`; after
+ * the first call of a size nothing is allocated and no stream or device is waited for (without
+ * d_ctrl_out the chain keeps the candidates in a buffer of its own, which grows only).  As
+ * sspp_job_set_queries itself, a call waits on the host for the previous set's host-to-device copy
+ * of the query tables (its staging's event: copies only, never a kernel) before it stages the next
+ * set.  The chain's single-query state stays as it was.  Q outside
+ * 1..64, or Q * B > 0x7fffffff: SSPP_E_INVAL.  B = 0: SSPP_OK, nothing written.
+ * sspp_chain_plan_many_host is SamplingPathPlanner::plan for Q >= 1 queries (any Q: chunks of at most
+ * 64 queries, fewer when a chunk's candidates would pass 256 MiB): query q's record and winner row
+ * are sspp_chain_plan_host(start_q, end_q, .., seeds[q])'s best_out and ctrl_out[best.index - first_id],
+ * bit for bit (with first_id = 0, the ids sspp_chain_plan_host scores).  One stream synchronisation;
+ * only the Q records and winner rows (and arc_out / feasible_out when asked for) leave the device.
+ * No reference counterpart (the reference plans one query per call). */
+int sspp_chain_sample_score_queries(sspp_chain* c, const double* knots, int degree, int Q,
+                                    const double* init_ctrl /* host [Q][n][dof] */, int n, int W,
+                                    const double* sigma /* [Q] */, const double* limits /* [Q][dof] */,
+                                    const uint64_t* seed /* [Q] */, int64_t first_id, int64_t B,
+                                    double* d_arc /* [Q][B] */, uint8_t* d_feasible /* [Q][B] */,
+                                    double* d_ctrl_out /* nullable [Q][B][n][dof] */,
+                                    sspp_best* d_best /* nullable [Q] */,
+                                    double* d_best_ctrl /* nullable [Q][n][dof] */, void* stream);
+int sspp_chain_plan_many_host(sspp_chain* c, int Q, const double* starts /* [Q][dof] */, const double* ends,
+                              double sigma, const double* limits /* [dof] */, int sample_count, int check_points,
+                              int init_points, const uint64_t* seeds /* [Q] */, int64_t first_id,
+                              double* knots_out /* [init_points + 4] */, sspp_best* best_out /* [Q] */,
+                              double* best_ctrl_out /* [Q][init_points][dof] */, int64_t* n_feasible /* [Q] */,
+                              double* arc_out /* nullable [Q][sample_count] */, uint8_t* feasible_out /* nullable */);
 
 /* ---- contact report for arms (DESIGN.md §5 "Contact report for arms") ----
  * Which pairs of a chain a pose or a path touches.  Columns: the chain's pair table in

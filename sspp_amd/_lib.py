@@ -163,6 +163,10 @@ SIGNATURES = {
                                              C.POINTER(Best)]),
     "sspp_chain_plan_host": (C.c_int, [_vp, _d, _d, C.c_double, _d, _i, _i, _i, C.c_uint64, _d, _d,
                                        C.POINTER(C.c_uint8), _d, C.POINTER(Best)]),
+    "sspp_chain_sample_score_queries": (C.c_int, [_vp, _d, _i, _i, _d, _i, _i, _d, _d, C.POINTER(C.c_uint64), _i64, _i64,
+                                                  _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sspp_chain_plan_many_host": (C.c_int, [_vp, _i, _d, _d, C.c_double, _d, _i, _i, _i, C.POINTER(C.c_uint64), _i64,
+                                            _d, C.POINTER(Best), _d, C.POINTER(_i64), _d, C.POINTER(C.c_uint8)]),
     "sspp_chain_static_pairs": (C.c_int, [_vp, C.POINTER(PairInfo), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _i,
                                           C.POINTER(C.c_int)]),
     "sspp_chain_pair_contacts": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),

@@ -14,6 +14,8 @@
 //                     semantics, no atomics).  A waypoint's coordinates are evaluated when a joint
 //                     asks for them, with eval_pt's products and fma order
 //   k_chain_best      findBestPath over the batch: lowest arc, lowest id on ties, the feasible count
+//   k_chain_best_q    the same per query of a query launch (one workgroup each), and the winner's
+//                     control points gathered into the query's row
 // Arc lengths and sampled candidates come from a scene-less SamplingPathPlanner job (k_sspp_c2f,
 // arc_all = 1): the existing code, bit for bit.
 #include "sspp_chain_dev.h"
@@ -139,6 +141,58 @@ __global__ __launch_bounds__(kBestBlock) void k_chain_best(const double* __restr
     }
 }
 
+// The same per query of a query launch, one workgroup each: k_chain_best's reduction over row q of
+// arc / feasible [Q][B], then the whole workgroup copies the winner's nd = n * D doubles from
+// ctrl [Q][B][nd] to best_ctrl [Q][nd] (zeros without a winner), lanes on consecutive words.  out
+// and best_ctrl are nullable and may be mapped pinned host memory (plain stores, each word once).
+__global__ __launch_bounds__(kBestBlock) void k_chain_best_q(const double* __restrict__ arc,
+                                                              const uint8_t* __restrict__ feasible,
+                                                              const double* __restrict__ ctrl, const long long B,
+                                                              const long long first_id, const int nd,
+                                                              sspp_best* __restrict__ out,
+                                                              double* __restrict__ best_ctrl) {
+    __shared__ double s_c[kBestBlock];
+    __shared__ long long s_i[kBestBlock], s_n[kBestBlock];
+    const long long q = blockIdx.x;
+    const double* qa = arc + q * B;
+    const uint8_t* qf = feasible + q * B;
+    double bc = INFINITY;
+    long long bi = -1, cnt = 0;
+    for (long long k = threadIdx.x; k < B; k += kBestBlock) {
+        if (!qf[k]) continue;
+        ++cnt;
+        const double a = qa[k];
+        if (a < bc) { bc = a; bi = k; }  // (ascending k per thread: the lowest id of equal arcs stays)
+    }
+    s_c[threadIdx.x] = bc; s_i[threadIdx.x] = bi; s_n[threadIdx.x] = cnt;
+    __syncthreads();
+    for (int s = kBestBlock / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) {
+            const double oc = s_c[threadIdx.x + s];
+            const long long oi = s_i[threadIdx.x + s];
+            if (oi >= 0 && (s_i[threadIdx.x] < 0 || oc < s_c[threadIdx.x] ||
+                            (oc == s_c[threadIdx.x] && oi < s_i[threadIdx.x]))) {
+                s_c[threadIdx.x] = oc;
+                s_i[threadIdx.x] = oi;
+            }
+            s_n[threadIdx.x] += s_n[threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    const long long win = s_i[0];  // (uniform: the loop's last barrier is behind every thread)
+    if (best_ctrl) {
+        const double* src = ctrl + ((size_t)q * (size_t)B + (size_t)(win >= 0 ? win : 0)) * (size_t)nd;
+        double* dst = best_ctrl + (size_t)q * (size_t)nd;
+        for (int t = threadIdx.x; t < nd; t += kBestBlock) dst[t] = win >= 0 ? src[t] : 0.0;
+    }
+    if (threadIdx.x == 0 && out) {
+        out[q].cost = win >= 0 ? s_c[0] : INFINITY;
+        out[q].index = win >= 0 ? first_id + win : -1;
+        out[q].count = s_n[0];
+        out[q].reserved = 0;
+    }
+}
+
 }  // namespace sspc
 
 extern "C" int sspp_chain_create(const sspp_model* m, int dof, int count_static, sspp_chain** out) {
@@ -153,7 +207,7 @@ extern "C" int sspp_chain_create(const sspp_model* m, int dof, int count_static,
     if (rc || (rc = c->d_bodies.upload(c->t.bodies.data(), c->t.bodies.size())) ||
         (rc = c->d_joints.upload(c->t.joints.data(), c->t.joints.size())) ||
         (rc = c->d_geoms.upload(c->t.geoms.data(), c->t.geoms.size())) ||
-        (rc = c->d_pairs.upload(c->t.pairs.data(), c->t.pairs.size())) || (rc = c->d_jobbest.reserve(1))) {
+        (rc = c->d_pairs.upload(c->t.pairs.data(), c->t.pairs.size())) || (rc = c->d_jobbest.reserve(kChainMaxQueries))) {
         delete c;
         return rc;
     }
@@ -311,6 +365,51 @@ extern "C" int sspp_chain_sample_score(sspp_chain* c, const double* knots, int d
     return chain_finish(c, d_ctrl_out, first_id, B, d_arc, d_feasible, d_best, (hipStream_t)stream);
 }
 
+// Q queries in one launch sequence (DESIGN.md §5 "Query launches for arms"): the scene-less job's
+// query launch samples every query's candidates and writes their arcs ([Q][B], a batch of Q * B to
+// the feasibility kernel), then one k_chain_best_q workgroup per query.  The job's single-query
+// state, and with it what sspp_chain_sample_score writes, stays as it was.
+extern "C" int sspp_chain_sample_score_queries(sspp_chain* c, const double* knots, int degree, int Q,
+                                               const double* init_ctrl, int n, int W, const double* sigma,
+                                               const double* limits, const uint64_t* seed, int64_t first_id,
+                                               int64_t B, double* d_arc, uint8_t* d_feasible, double* d_ctrl_out,
+                                               sspp_best* d_best, double* d_best_ctrl, void* stream) {
+    sspp::clear_error();
+    if (!c) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_sample_score_queries: null chain");
+    if (Q < 1 || Q > kChainMaxQueries)
+        return sspp::set_error(SSPP_E_INVAL, "sspp_chain_sample_score_queries: 1..64 queries, got " + std::to_string(Q));
+    if (B < 0) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_sample_score_queries: negative batch");
+    if (B == 0) return SSPP_OK;
+    if (!init_ctrl || !sigma || !limits || !seed || !d_arc || !d_feasible)
+        return sspp::set_error(SSPP_E_INVAL, "sspp_chain_sample_score_queries: null argument");
+    if (B > 0x7fffffffll / Q)
+        return sspp::set_error(SSPP_E_INVAL, "sspp_chain_sample_score_queries: too many candidates for one launch");
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if ((rc = chain_job(c, knots, degree, n, W, B))) return rc;
+    const size_t nd = (size_t)n * c->t.D;
+    if (!d_ctrl_out) {  // the feasibility kernel and the winner gather read the candidates
+        const size_t need = (size_t)Q * (size_t)B * nd;
+        if (need > c->d_qctrl.n) {
+            (void)hipDeviceSynchronize();  // (an earlier launch may still read the smaller buffer)
+            if ((rc = c->d_qctrl.reserve(need))) return rc;
+        }
+        d_ctrl_out = c->d_qctrl.p;
+    }
+    if ((rc = sspp_job_set_queries(c->job, Q, init_ctrl, sigma, limits, seed, stream)) ||
+        (rc = sspp_job_sample_score_queries(c->job, first_id, B, d_arc, d_feasible, d_ctrl_out, c->d_jobbest.p, stream)))
+        return rc;
+    const ChainT T = c->view();
+    const sspp_job* j = c->job;
+    hipLaunchKernelGGL(k_chain_feas, dim3((int)(Q * B)), dim3(kChainBlock), chain_lds(T.nd), st, T, c->static_block(),
+                       j->p, j->n, j->W, j->d_tab.p, j->d_span.p, d_ctrl_out, d_arc, d_feasible);
+    if ((rc = sspo::hip_fail(hipGetLastError(), "k_chain_feas query launch"))) return rc;
+    if (!d_best && !d_best_ctrl) return SSPP_OK;
+    hipLaunchKernelGGL(k_chain_best_q, dim3(Q), dim3(kBestBlock), 0, st, d_arc, d_feasible, d_ctrl_out, (long long)B,
+                       (long long)first_id, (int)nd, d_best, d_best_ctrl);
+    return sspo::hip_fail(hipGetLastError(), "k_chain_best_q launch");
+}
+
 // ---- the same on host buffers (the drop-in planner of an articulated model): staged to the device,
 // run by the calls above and copied back on the drop-in planners' shared stream, which alone is waited for
 extern "C" int sspp_chain_contacts_host(const sspp_chain* c, const double* q, int64_t N, uint8_t* hit) {
@@ -393,4 +492,79 @@ extern "C" int sspp_chain_plan_host(sspp_chain* c, const double* start, const do
                                  d_f.p, d_ctrl.p, d_b.p, st);
     if (!rc && ctrl_out) rc = hip_fail(hipMemcpyAsync(ctrl_out, d_ctrl.p, sizeof(double) * nc, hipMemcpyDeviceToHost, st), "copy candidates");
     return chain_read_back(st, rc, B, d_arc, d_f, d_b, arc_out, feasible_out, best_out);
+}
+
+// device bytes of one chunk's candidates: larger sets go in chunks of fewer queries (sspp_planner_plan_many's cap)
+constexpr size_t kChainManyCtrlBytes = (size_t)256 << 20;
+
+// SamplingPathPlanner::plan for Q queries of one arm: initializePath per query on the host, then per
+// chunk of at most kChainMaxQueries queries one sspp_chain_sample_score_queries whose k_chain_best_q
+// writes the records and the winners' rows straight into the chain's mapped pinned memory (Q rows;
+// no candidate leaves the device), one stream synchronisation at the end.
+extern "C" int sspp_chain_plan_many_host(sspp_chain* c, int Q, const double* starts, const double* ends, double sigma,
+                                         const double* limits, int sample_count, int check_points, int init_points,
+                                         const uint64_t* seeds, int64_t first_id, double* knots_out,
+                                         sspp_best* best_out, double* best_ctrl_out, int64_t* n_feasible,
+                                         double* arc_out, uint8_t* feasible_out) {
+    sspp::clear_error();
+    if (!c || !starts || !ends || !limits || !seeds || !knots_out || !best_out || !best_ctrl_out || !n_feasible)
+        return sspp::set_error(SSPP_E_INVAL, "sspp_chain_plan_many_host: null argument");
+    if (Q < 1) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_plan_many_host: Q must be >= 1");
+    const int n = init_points, D = c->t.D, deg = 3;
+    if (sample_count < 1) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_plan_many_host: sample_count must be >= 1");
+    if (n < deg + 1)
+        return sspp::set_error(SSPP_E_INVAL, "sspp_chain_plan_many_host: init_points must be >= 4 for a cubic spline");
+    if (check_points < 2) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_plan_many_host: check_points must be >= 2");
+    // initializePath per query (include/sspp.h:82-97); the knot vector depends on n only
+    const size_t nd = (size_t)n * D;
+    const int64_t B = sample_count;
+    std::vector<double> u((size_t)n), pts(nd), ctrl0((size_t)Q * nd);
+    for (int i = 0; i < n; ++i) u[i] = (double)i / (n - 1);
+    for (int q = 0; q < Q; ++q) {
+        for (int i = 0; i < n; ++i) {
+            const double t = u[i];
+            for (int d = 0; d < D; ++d)
+                pts[(size_t)i * D + d] = (1 - t) * starts[(size_t)q * D + d] + t * ends[(size_t)q * D + d];
+        }
+        if (sspp::interpolate(pts.data(), n, D, deg, u.data(), knots_out, ctrl0.data() + q * nd) != 0)
+            return sspp::set_error(SSPP_E_INVAL, "initializePath: interpolation failed");
+    }
+    const int chunk = (int)std::min<size_t>(kChainMaxQueries,
+                                            std::max<size_t>(1, kChainManyCtrlBytes / (sizeof(double) * (size_t)B * nd)));
+    const int qc_max = std::min(Q, chunk);
+    hipStream_t st = (hipStream_t)sspp::shared_stream(0);
+    int rc;
+    if ((rc = c->dm_arc.reserve((size_t)qc_max * B)) || (rc = c->dm_feas.reserve((size_t)qc_max * B)) ||
+        (rc = c->hm_best.reserve((size_t)Q)) || (rc = c->hm_ctrl.reserve((size_t)Q * nd)) ||
+        (arc_out && (rc = c->hm_arc.reserve((size_t)Q * B))) || (feasible_out && (rc = c->hm_feas.reserve((size_t)Q * B))))
+        return rc;
+    sspp_best* hb = c->hm_best.dev();
+    double* hc = c->hm_ctrl.dev();
+    if (!hb || !hc) return sspp::set_error(SSPP_E_HIP, "hipHostGetDevicePointer failed");
+    std::vector<double> sig((size_t)qc_max, sigma), lim((size_t)qc_max * D);
+    for (int q = 0; q < qc_max; ++q) std::memcpy(lim.data() + (size_t)q * D, limits, sizeof(double) * D);
+    rc = SSPP_OK;
+    for (int q0 = 0; q0 < Q && !rc; q0 += chunk) {
+        const int qc = std::min(chunk, Q - q0);
+        rc = sspp_chain_sample_score_queries(c, knots_out, deg, qc, ctrl0.data() + (size_t)q0 * nd, n, check_points,
+                                             sig.data(), lim.data(), seeds + q0, first_id, B, c->dm_arc.p, c->dm_feas.p,
+                                             nullptr, hb + q0, hc + (size_t)q0 * nd, st);
+        if (!rc && arc_out)
+            rc = hip_fail(hipMemcpyAsync(c->hm_arc.p + (size_t)q0 * B, c->dm_arc.p, sizeof(double) * qc * B,
+                                         hipMemcpyDeviceToHost, st), "copy arc");
+        if (!rc && feasible_out)
+            rc = hip_fail(hipMemcpyAsync(c->hm_feas.p + (size_t)q0 * B, c->dm_feas.p, (size_t)qc * B,
+                                         hipMemcpyDeviceToHost, st), "copy feasible");
+    }
+    const std::string why = rc ? sspp_last_error() : "";
+    const int rs = hip_fail(hipStreamSynchronize(st), "sspp_chain_plan_many_host");  // (also after a failure: work is queued)
+    if (rc) return sspp::set_error(rc, why);
+    if (rs) return rs;
+    if ((rc = sspp_best_check(c->hm_best.p, Q))) return rc;
+    std::memcpy(best_out, c->hm_best.p, sizeof(sspp_best) * Q);
+    std::memcpy(best_ctrl_out, c->hm_ctrl.p, sizeof(double) * Q * nd);
+    for (int q = 0; q < Q; ++q) n_feasible[q] = best_out[q].count;
+    if (arc_out) std::memcpy(arc_out, c->hm_arc.p, sizeof(double) * Q * B);
+    if (feasible_out) std::memcpy(feasible_out, c->hm_feas.p, (size_t)Q * B);
+    return SSPP_OK;
 }

@@ -7,6 +7,7 @@
 namespace sspc {
 
 constexpr int kChainBlock = 64;  // one wave: the frames' LDS is per lane, nothing is shared
+constexpr int kChainMaxQueries = 64;  // queries of one query launch (sspp_job_set_queries' limit)
 
 struct ChainT {
     const CBody* __restrict__ bodies;
@@ -42,7 +43,17 @@ struct sspp_chain {
     int job_p = 0, job_n = 0, job_W = 0;
     int64_t job_cap = 0;
     sspo::Dev<double> d_ctrl;
-    sspo::Dev<sspp_best> d_jobbest;
+    sspo::Dev<sspp_best> d_jobbest;  // kChainMaxQueries records: a query launch's job writes one per query
+    // query launches (sspp_chain_sample_score_queries): the candidates [Q][B][n][D] of a launch
+    // without d_ctrl_out.  sspp_chain_plan_many_host: one chunk's device outputs, and the whole
+    // call's results in pinned memory (records and winner rows mapped: k_chain_best_q writes them)
+    sspo::Dev<double> d_qctrl;
+    sspo::Dev<double> dm_arc;
+    sspo::Dev<uint8_t> dm_feas;
+    sspo::Pinned<sspp_best> hm_best{hipHostMallocMapped | hipHostMallocCoherent};
+    sspo::Pinned<double> hm_ctrl{hipHostMallocMapped | hipHostMallocCoherent};
+    sspo::Pinned<double> hm_arc;
+    sspo::Pinned<uint8_t> hm_feas;
     ~sspp_chain() {
         if (job) sspp_job_free(job);
     }

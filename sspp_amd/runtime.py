@@ -458,6 +458,65 @@ class Chain:
                                             _ptr(feasible), _ptr(ctrl_out), _ptr(best), _stream(stream)),
               "chain sample_score")
 
+    def sample_score_queries(self, knots, degree, init_ctrl, sigma, limits, seeds, check_points, first_id, B, arc,
+                             feasible, best=None, ctrl_out=None, best_ctrl=None, stream=None):
+        """Q queries in one launch sequence (sspp_chain_sample_score_queries): init_ctrl (Q, n, dof),
+        sigma (Q,), limits (Q, dof), seeds (Q,).  Row q of the device tensors arc / feasible (Q, B),
+        ctrl_out (Q, B, n, dof), best (Q, 4) and best_ctrl (Q, n, dof, the winner's control points,
+        zeros without one) is what sample_score writes for query q alone.  Asynchronous."""
+        knots = _f64(knots)
+        init_ctrl = np.ascontiguousarray(np.asarray(init_ctrl, dtype=np.float64))
+        if init_ctrl.ndim != 3 or init_ctrl.shape[2] != self.dof:
+            raise ValueError("init_ctrl must be (Q, n, %d), got %s" % (self.dof, init_ctrl.shape))
+        Q, n = int(init_ctrl.shape[0]), int(init_ctrl.shape[1])
+        sigma = _f64(sigma, Q)
+        limits = np.ascontiguousarray(np.asarray(limits, dtype=np.float64))
+        if limits.shape != (Q, self.dof):
+            raise ValueError("limits must be (%d, %d), got %s" % (Q, self.dof, limits.shape))
+        seeds = np.ascontiguousarray(np.asarray([int(s) & (2 ** 64 - 1) for s in np.asarray(seeds).reshape(-1)],
+                                                dtype=np.uint64))
+        if seeds.size != Q:
+            raise ValueError("expected %d seeds, got %d" % (Q, seeds.size))
+        check(lib().sspp_chain_sample_score_queries(self._h, _dptr(knots), int(degree), Q, _dptr(init_ctrl), n,
+                                                    int(check_points), _dptr(sigma), _dptr(limits),
+                                                    seeds.ctypes.data_as(C.POINTER(C.c_uint64)), int(first_id), int(B),
+                                                    _ptr(arc), _ptr(feasible), _ptr(ctrl_out), _ptr(best),
+                                                    _ptr(best_ctrl), _stream(stream)), "chain sample_score_queries")
+
+    def plan_many(self, starts, ends, sigma, limits, sample_count, check_points, init_points, seeds=None, first_id=0,
+                  return_all=False):
+        """SamplingPathPlanner::plan for Q queries of this arm in one call (sspp_chain_plan_many_host):
+        starts / ends (Q, dof); sigma, limits and the shape are shared; seeds (Q,), DEFAULT_SEED each
+        when None.  Returns dict(knots, best = Q tuples (cost, index, count), best_ctrl (Q, n, dof),
+        n_feasible (Q,)), with return_all also arc (Q, sample_count) and feasible (Q, sample_count).
+        Query q's record and winner row are those of a plan of (starts[q], ends[q], seeds[q]) alone."""
+        starts = np.ascontiguousarray(np.asarray(starts, dtype=np.float64))
+        ends = np.ascontiguousarray(np.asarray(ends, dtype=np.float64))
+        if starts.ndim != 2 or starts.shape[1] != self.dof or ends.shape != starts.shape:
+            raise ValueError("starts and ends must be (Q, %d), got %s and %s" % (self.dof, starts.shape, ends.shape))
+        Q, n, B = int(starts.shape[0]), int(init_points), int(sample_count)
+        lim = _f64(limits, self.dof)
+        seeds = [DEFAULT_SEED] * Q if seeds is None else list(np.asarray(seeds).reshape(-1))
+        seeds = np.ascontiguousarray(np.asarray([int(s) & (2 ** 64 - 1) for s in seeds], dtype=np.uint64))
+        if seeds.size != Q:
+            raise ValueError("expected %d seeds, got %d" % (Q, seeds.size))
+        knots = np.zeros(max(n, 0) + 4)
+        best = (Best * max(Q, 1))()
+        best_ctrl = np.zeros((Q, max(n, 0), self.dof))
+        nf = np.zeros(max(Q, 1), dtype=np.int64)
+        arc = np.zeros((Q, max(B, 0))) if return_all else None
+        feas = np.zeros((Q, max(B, 0)), dtype=np.uint8) if return_all else None
+        check(lib().sspp_chain_plan_many_host(
+            self._h, Q, _dptr(starts), _dptr(ends), float(sigma), _dptr(lim), B, int(check_points), n,
+            seeds.ctypes.data_as(C.POINTER(C.c_uint64)), int(first_id), _dptr(knots), best, _dptr(best_ctrl),
+            nf.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(arc) if return_all else None,
+            feas.ctypes.data_as(C.POINTER(C.c_uint8)) if return_all else None), "chain plan_many")
+        out = dict(knots=knots, best=[(float(b.cost), int(b.index), int(b.count)) for b in best[:Q]], best_ctrl=best_ctrl,
+                   n_feasible=nf[:Q].copy())
+        if return_all:
+            out["arc"], out["feasible"] = arc, feas
+        return out
+
 
 def interpolate(pts, degree, u):
     """Eigen SplineFitting::Interpolate (include/sspp.h:95): returns (knots, ctrl [n][D])."""
