@@ -59,6 +59,10 @@ int span_of(double u, int p, const double* knots, int nknots);
 void basis_funcs(double u, int p, const double* knots, int nknots, double* N);
 int interpolate(const double* pts, int n, int D, int p, const double* u, double* knots,
                 double* ctrl);
+// SamplingPathPlanner's initializePath (include/sspp.h:82-97): linear via points from start to end
+// [D] at t_i = i / (n - 1), interpolated: knots [n + p + 1] and control points [n][D].  SSPP_OK, or
+// SSPP_E_INVAL with the message set
+int initialize_path(const double* start, const double* end, int n, int D, int p, double* knots, double* ctrl);
 // Householder QR "program" of the collocation matrix for fixed parameters u (PathModel::fromVias
 // precompute): [n][n] reflectors | [n] |v|^2 | [n][n] R; qr_apply replays it on B [n][D]
 int qr_program(const double* u, int n, int p, double* knots, double* prog);

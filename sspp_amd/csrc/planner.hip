@@ -130,16 +130,9 @@ static int plan_enqueue(sspp_planner* p, const double* start, const double* end,
     if (sample_count < 1) return sspp::set_error(SSPP_E_INVAL, "sample_count must be >= 1");
     if (n < deg + 1) return sspp::set_error(SSPP_E_INVAL, "init_points must be >= 4 for a cubic spline");
     if (check_points < 2) return sspp::set_error(SSPP_E_INVAL, "check_points must be >= 2");
-    // initializePath (include/sspp.h:82-97): linear via points at t_i = i / (n - 1)
-    std::vector<double> u((size_t)n), pts((size_t)n * D), ctrl0((size_t)n * D);
-    for (int i = 0; i < n; ++i) {
-        const double t = (double)i / (n - 1);
-        u[i] = t;
-        for (int d = 0; d < D; ++d) pts[(size_t)i * D + d] = (1 - t) * start[d] + t * end[d];
-    }
-    if (sspp::interpolate(pts.data(), n, D, deg, u.data(), knots_out, ctrl0.data()) != 0)
-        return sspp::set_error(SSPP_E_INVAL, "initializePath: interpolation failed");
+    std::vector<double> ctrl0((size_t)n * D);
     int rc;
+    if ((rc = sspp::initialize_path(start, end, n, D, deg, knots_out, ctrl0.data()))) return rc;
     const size_t nd = (size_t)n * D;
     const int64_t B = sample_count;
     if (!p->plan_job.j || p->plan_n != n || p->plan_W != check_points || B > p->plan_cap) {
@@ -243,20 +236,17 @@ extern "C" int sspp_planner_plan_many(sspp_planner* p, int Q, const double* star
     if (sample_count < 1) return sspp::set_error(SSPP_E_INVAL, "sample_count must be >= 1");
     if (n < deg + 1) return sspp::set_error(SSPP_E_INVAL, "init_points must be >= 4 for a cubic spline");
     if (check_points < 2) return sspp::set_error(SSPP_E_INVAL, "check_points must be >= 2");
-    // initializePath per query (include/sspp.h:82-97); the knot vector depends on n only
+    // initializePath per query; the knot vector depends on n only
     const size_t nd = (size_t)n * D;
     const int64_t B = sample_count;
-    std::vector<double> u((size_t)n), pts(nd), ctrl0((size_t)Q * nd);
-    for (int i = 0; i < n; ++i) u[i] = (double)i / (n - 1);
-    for (int q = 0; q < Q; ++q) {
-        for (int i = 0; i < n; ++i)
-            for (int d = 0; d < D; ++d) pts[(size_t)i * D + d] = (1 - u[i]) * starts[(size_t)q * D + d] + u[i] * ends[(size_t)q * D + d];
-        if (sspp::interpolate(pts.data(), n, D, deg, u.data(), knots_out, ctrl0.data() + q * nd) != 0)
-            return sspp::set_error(SSPP_E_INVAL, "initializePath: interpolation failed");
-    }
+    std::vector<double> ctrl0((size_t)Q * nd);
+    int rc;
+    for (int q = 0; q < Q; ++q)
+        if ((rc = sspp::initialize_path(starts + (size_t)q * D, ends + (size_t)q * D, n, D, deg, knots_out,
+                                        ctrl0.data() + q * nd)))
+            return rc;
     const int chunk = (int)std::min<size_t>(64, std::max<size_t>(1, kManyCtrlBytes / (sizeof(double) * (size_t)B * nd)));
     const int qc_max = std::min(Q, chunk);
-    int rc;
     if (!p->many_job.j || p->many_n != n || p->many_W != check_points || B > p->many_cap) {
         p->many_job.reset();
         sspp_sspp_args a{};

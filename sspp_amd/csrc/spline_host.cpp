@@ -140,6 +140,18 @@ int interpolate(const double* pts, int n, int D, int p, const double* u, double*
     return 0;
 }
 
+int initialize_path(const double* start, const double* end, int n, int D, int p, double* knots, double* ctrl) {
+    std::vector<double> u((size_t)n), pts((size_t)n * D);
+    for (int i = 0; i < n; ++i) {
+        const double t = (double)i / (n - 1);
+        u[i] = t;
+        for (int d = 0; d < D; ++d) pts[(size_t)i * D + d] = (1 - t) * start[d] + t * end[d];
+    }
+    if (interpolate(pts.data(), n, D, p, u.data(), knots, ctrl) != 0)
+        return set_error(SSPP_E_INVAL, "initializePath: interpolation failed");
+    return SSPP_OK;
+}
+
 int qr_program(const double* u, int n, int p, double* knots, double* prog) {
     if (n < p + 1 || p < 1 || p > 15) return -1;
     knot_averaging(u, n, p, knots);

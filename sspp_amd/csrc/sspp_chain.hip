@@ -13,8 +13,8 @@
 //                     after each pass: a candidate stops at its first contact (checkCollision's
 //                     semantics, no atomics).  A waypoint's coordinates are evaluated when a joint
 //                     asks for them, with eval_pt's products and fma order
-//   k_chain_best      findBestPath over the batch: lowest arc, lowest id on ties, the feasible count
-//   k_chain_best_q    the same per query of a query launch (one workgroup each), and the winner's
+//   k_chain_best_q    findBestPath over a batch, one workgroup: lowest arc, lowest id on ties, the
+//                     feasible count; in a query launch one workgroup per query, and the winner's
 //                     control points gathered into the query's row
 // Arc lengths and sampled candidates come from a scene-less SamplingPathPlanner job (k_sspp_c2f,
 // arc_all = 1): the existing code, bit for bit.
@@ -103,48 +103,12 @@ __global__ __launch_bounds__(kChainBlock) void k_chain_feas(const ChainT T, cons
     }
 }
 
-// findBestPath over B candidates in one workgroup: (arc, id) minimum over the feasible ones
+// findBestPath per row q of arc / feasible [Q][B], one workgroup each: the (arc, id) minimum over
+// the feasible candidates and their count, then the whole workgroup copies the winner's nd = n * D
+// doubles from ctrl [Q][B][nd] to best_ctrl [Q][nd] (zeros without a winner), lanes on consecutive
+// words.  out and best_ctrl are nullable (a single query: one workgroup, no best_ctrl) and may be
+// mapped pinned host memory (plain stores, each word once).
 constexpr int kBestBlock = 256;
-__global__ __launch_bounds__(kBestBlock) void k_chain_best(const double* __restrict__ arc,
-                                                            const uint8_t* __restrict__ feasible, const long long B,
-                                                            const long long first_id, sspp_best* __restrict__ out) {
-    __shared__ double s_c[kBestBlock];
-    __shared__ long long s_i[kBestBlock], s_n[kBestBlock];
-    double bc = INFINITY;
-    long long bi = -1, cnt = 0;
-    for (long long k = threadIdx.x; k < B; k += kBestBlock) {
-        if (!feasible[k]) continue;
-        ++cnt;
-        const double a = arc[k];
-        if (a < bc) { bc = a; bi = k; }  // (ascending k per thread: the lowest id of equal arcs stays)
-    }
-    s_c[threadIdx.x] = bc; s_i[threadIdx.x] = bi; s_n[threadIdx.x] = cnt;
-    __syncthreads();
-    for (int s = kBestBlock / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) {
-            const double oc = s_c[threadIdx.x + s];
-            const long long oi = s_i[threadIdx.x + s];
-            if (oi >= 0 && (s_i[threadIdx.x] < 0 || oc < s_c[threadIdx.x] ||
-                            (oc == s_c[threadIdx.x] && oi < s_i[threadIdx.x]))) {
-                s_c[threadIdx.x] = oc;
-                s_i[threadIdx.x] = oi;
-            }
-            s_n[threadIdx.x] += s_n[threadIdx.x + s];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        out->cost = s_i[0] >= 0 ? s_c[0] : INFINITY;
-        out->index = s_i[0] >= 0 ? first_id + s_i[0] : -1;
-        out->count = s_n[0];
-        out->reserved = 0;
-    }
-}
-
-// The same per query of a query launch, one workgroup each: k_chain_best's reduction over row q of
-// arc / feasible [Q][B], then the whole workgroup copies the winner's nd = n * D doubles from
-// ctrl [Q][B][nd] to best_ctrl [Q][nd] (zeros without a winner), lanes on consecutive words.  out
-// and best_ctrl are nullable and may be mapped pinned host memory (plain stores, each word once).
 __global__ __launch_bounds__(kBestBlock) void k_chain_best_q(const double* __restrict__ arc,
                                                               const uint8_t* __restrict__ feasible,
                                                               const double* __restrict__ ctrl, const long long B,
@@ -246,13 +210,6 @@ extern "C" int sspp_chain_pairs(const sspp_chain* c, sspp_pair_info* out, int ca
     return SSPP_OK;
 }
 
-static int chain_blocks(int64_t items, int* out) {
-    const int64_t nblk = (items + kChainBlock - 1) / kChainBlock;
-    if (nblk > 0x7fffffffll) return sspp::set_error(SSPP_E_INVAL, "sspp_chain: too many poses for one launch");
-    *out = (int)nblk;
-    return SSPP_OK;
-}
-
 extern "C" int sspp_chain_fk(const sspp_chain* c, const double* d_q, int64_t N, double* d_gpos, double* d_gmat,
                              void* stream) {
     sspp::clear_error();
@@ -261,7 +218,7 @@ extern "C" int sspp_chain_fk(const sspp_chain* c, const double* d_q, int64_t N, 
     if (N == 0 || c->t.geoms.empty()) return SSPP_OK;
     if (!d_q || !d_gpos || !d_gmat) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_fk: null poses / output");
     int nblk = 0;
-    if (int rc = chain_blocks(N, &nblk)) return rc;
+    if (int rc = chain_blocks(N, "sspp_chain", &nblk)) return rc;
     const ChainT T = c->view();
     hipLaunchKernelGGL(k_chain_fk, dim3(nblk), dim3(kChainBlock), chain_lds(T.nd), (hipStream_t)stream, T, d_q,
                        (long long)N, d_gpos, d_gmat);
@@ -275,7 +232,7 @@ extern "C" int sspp_chain_contacts(const sspp_chain* c, const double* d_q, int64
     if (N == 0) return SSPP_OK;
     if (!d_q || !d_hit) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_contacts: null poses / output");
     int nblk = 0;
-    if (int rc = chain_blocks(N, &nblk)) return rc;
+    if (int rc = chain_blocks(N, "sspp_chain", &nblk)) return rc;
     const ChainT T = c->view();
     hipLaunchKernelGGL(k_chain_contacts, dim3(nblk), dim3(kChainBlock), chain_lds(T.nd), (hipStream_t)stream, T,
                        c->static_block(), d_q, (long long)N, d_hit);
@@ -311,21 +268,21 @@ int sspc::chain_job(sspp_chain* c, const double* knots, int degree, int n, int W
     return SSPP_OK;
 }
 
-// feasibility of the candidates in d_ctrl over the job's arcs, then the argmin
-static int chain_finish(sspp_chain* c, const double* d_ctrl, int64_t first_id, int64_t B, double* d_arc,
-                        uint8_t* d_feasible, sspp_best* d_best, hipStream_t st) {
-    if (B > 0x7fffffffll) return sspp::set_error(SSPP_E_INVAL, "sspp_chain: too many candidates for one launch");
+// feasibility of the Q * B candidates in d_ctrl ([Q][B][n][D]) over the job's arcs, then the argmin
+// per row of B and, with d_best_ctrl, the winners' rows (many: a query launch, in a failure's message)
+static int chain_finish(sspp_chain* c, const double* d_ctrl, int64_t first_id, int Q, int64_t B, double* d_arc,
+                        uint8_t* d_feasible, sspp_best* d_best, double* d_best_ctrl, bool many, hipStream_t st) {
+    if (B > 0x7fffffffll)  // (a query launch has checked Q * B)
+        return sspp::set_error(SSPP_E_INVAL, "sspp_chain: too many candidates for one launch");
     const ChainT T = c->view();
     const sspp_job* j = c->job;
-    hipLaunchKernelGGL(k_chain_feas, dim3((int)B), dim3(kChainBlock), chain_lds(T.nd), st, T, c->static_block(), j->p,
-                       j->n, j->W, j->d_tab.p, j->d_span.p, d_ctrl, d_arc, d_feasible);
-    if (int rc = sspo::hip_fail(hipGetLastError(), "k_chain_feas launch")) return rc;
-    if (d_best) {
-        hipLaunchKernelGGL(k_chain_best, dim3(1), dim3(kBestBlock), 0, st, d_arc, d_feasible, (long long)B,
-                           (long long)first_id, d_best);
-        return sspo::hip_fail(hipGetLastError(), "k_chain_best launch");
-    }
-    return SSPP_OK;
+    hipLaunchKernelGGL(k_chain_feas, dim3((int)(Q * B)), dim3(kChainBlock), chain_lds(T.nd), st, T, c->static_block(),
+                       j->p, j->n, j->W, j->d_tab.p, j->d_span.p, d_ctrl, d_arc, d_feasible);
+    if (int rc = sspo::hip_fail(hipGetLastError(), many ? "k_chain_feas query launch" : "k_chain_feas launch")) return rc;
+    if (!d_best && !d_best_ctrl) return SSPP_OK;
+    hipLaunchKernelGGL(k_chain_best_q, dim3(Q), dim3(kBestBlock), 0, st, d_arc, d_feasible, d_ctrl, (long long)B,
+                       (long long)first_id, j->n * T.D, d_best, d_best_ctrl);
+    return sspo::hip_fail(hipGetLastError(), many ? "k_chain_best_q launch" : "k_chain_best launch");
 }
 
 extern "C" int sspp_chain_score_ctrl(sspp_chain* c, const double* knots, int degree, const double* d_ctrl,
@@ -340,7 +297,7 @@ extern "C" int sspp_chain_score_ctrl(sspp_chain* c, const double* knots, int deg
     if ((rc = chain_job(c, knots, degree, n, W, B)) ||
         (rc = sspp_job_score_ctrl(c->job, d_ctrl, first_id, B, d_arc, d_feasible, c->d_jobbest.p, stream)))
         return rc;
-    return chain_finish(c, d_ctrl, first_id, B, d_arc, d_feasible, d_best, (hipStream_t)stream);
+    return chain_finish(c, d_ctrl, first_id, 1, B, d_arc, d_feasible, d_best, nullptr, false, (hipStream_t)stream);
 }
 
 extern "C" int sspp_chain_sample_score(sspp_chain* c, const double* knots, int degree, const double* init_ctrl, int n,
@@ -362,7 +319,7 @@ extern "C" int sspp_chain_sample_score(sspp_chain* c, const double* knots, int d
     if ((rc = sspp_job_update_sspp(c->job, init_ctrl, sigma, limits, seed, stream)) ||
         (rc = sspp_job_sample_score(c->job, first_id, B, d_arc, d_feasible, d_ctrl_out, c->d_jobbest.p, stream)))
         return rc;
-    return chain_finish(c, d_ctrl_out, first_id, B, d_arc, d_feasible, d_best, (hipStream_t)stream);
+    return chain_finish(c, d_ctrl_out, first_id, 1, B, d_arc, d_feasible, d_best, nullptr, false, (hipStream_t)stream);
 }
 
 // Q queries in one launch sequence (DESIGN.md §5 "Query launches for arms"): the scene-less job's
@@ -384,12 +341,10 @@ extern "C" int sspp_chain_sample_score_queries(sspp_chain* c, const double* knot
         return sspp::set_error(SSPP_E_INVAL, "sspp_chain_sample_score_queries: null argument");
     if (B > 0x7fffffffll / Q)
         return sspp::set_error(SSPP_E_INVAL, "sspp_chain_sample_score_queries: too many candidates for one launch");
-    hipStream_t st = (hipStream_t)stream;
     int rc;
     if ((rc = chain_job(c, knots, degree, n, W, B))) return rc;
-    const size_t nd = (size_t)n * c->t.D;
     if (!d_ctrl_out) {  // the feasibility kernel and the winner gather read the candidates
-        const size_t need = (size_t)Q * (size_t)B * nd;
+        const size_t need = (size_t)Q * (size_t)B * n * c->t.D;
         if (need > c->d_qctrl.n) {
             (void)hipDeviceSynchronize();  // (an earlier launch may still read the smaller buffer)
             if ((rc = c->d_qctrl.reserve(need))) return rc;
@@ -399,15 +354,7 @@ extern "C" int sspp_chain_sample_score_queries(sspp_chain* c, const double* knot
     if ((rc = sspp_job_set_queries(c->job, Q, init_ctrl, sigma, limits, seed, stream)) ||
         (rc = sspp_job_sample_score_queries(c->job, first_id, B, d_arc, d_feasible, d_ctrl_out, c->d_jobbest.p, stream)))
         return rc;
-    const ChainT T = c->view();
-    const sspp_job* j = c->job;
-    hipLaunchKernelGGL(k_chain_feas, dim3((int)(Q * B)), dim3(kChainBlock), chain_lds(T.nd), st, T, c->static_block(),
-                       j->p, j->n, j->W, j->d_tab.p, j->d_span.p, d_ctrl_out, d_arc, d_feasible);
-    if ((rc = sspo::hip_fail(hipGetLastError(), "k_chain_feas query launch"))) return rc;
-    if (!d_best && !d_best_ctrl) return SSPP_OK;
-    hipLaunchKernelGGL(k_chain_best_q, dim3(Q), dim3(kBestBlock), 0, st, d_arc, d_feasible, d_ctrl_out, (long long)B,
-                       (long long)first_id, (int)nd, d_best, d_best_ctrl);
-    return sspo::hip_fail(hipGetLastError(), "k_chain_best_q launch");
+    return chain_finish(c, d_ctrl_out, first_id, Q, B, d_arc, d_feasible, d_best, d_best_ctrl, true, (hipStream_t)stream);
 }
 
 // ---- the same on host buffers (the drop-in planner of an articulated model): staged to the device,
@@ -424,8 +371,7 @@ extern "C" int sspp_chain_contacts_host(const sspp_chain* c, const double* q, in
     rc = hip_fail(hipMemcpyAsync(d_q.p, q, sizeof(double) * nq, hipMemcpyHostToDevice, st), "copy poses");
     if (!rc) rc = sspp_chain_contacts(c, d_q.p, N, d_h.p, st);
     if (!rc) rc = hip_fail(hipMemcpyAsync(hit, d_h.p, (size_t)N, hipMemcpyDeviceToHost, st), "copy hits");
-    const int rs = hip_fail(hipStreamSynchronize(st), "sspp_chain_contacts_host");
-    return rc ? rc : rs;
+    return chain_wait(st, rc, "sspp_chain_contacts_host");
 }
 
 static int chain_read_back(hipStream_t st, int rc, int64_t B, const Dev<double>& d_arc, const Dev<uint8_t>& d_f,
@@ -433,8 +379,7 @@ static int chain_read_back(hipStream_t st, int rc, int64_t B, const Dev<double>&
     if (!rc && arc_out) rc = hip_fail(hipMemcpyAsync(arc_out, d_arc.p, sizeof(double) * B, hipMemcpyDeviceToHost, st), "copy arc");
     if (!rc && feasible_out) rc = hip_fail(hipMemcpyAsync(feasible_out, d_f.p, (size_t)B, hipMemcpyDeviceToHost, st), "copy feasible");
     if (!rc && best_out) rc = hip_fail(hipMemcpyAsync(best_out, d_b.p, sizeof(sspp_best), hipMemcpyDeviceToHost, st), "copy best");
-    const int rs = hip_fail(hipStreamSynchronize(st), "sspp_chain host call");
-    return rc ? rc : rs;
+    return chain_wait(st, rc, "sspp_chain host call");
 }
 
 extern "C" int sspp_chain_score_ctrl_host(sspp_chain* c, const double* knots, int degree, const double* ctrl, int64_t B,
@@ -469,22 +414,15 @@ extern "C" int sspp_chain_plan_host(sspp_chain* c, const double* start, const do
     if (sample_count < 1) return sspp::set_error(SSPP_E_INVAL, "sample_count must be >= 1");
     if (n < deg + 1) return sspp::set_error(SSPP_E_INVAL, "init_points must be >= 4 for a cubic spline");
     if (check_points < 2) return sspp::set_error(SSPP_E_INVAL, "check_points must be >= 2");
-    // initializePath (include/sspp.h:82-97): linear via points at t_i = i / (n - 1)
-    std::vector<double> u((size_t)n), pts((size_t)n * D), ctrl0((size_t)n * D);
-    for (int i = 0; i < n; ++i) {
-        const double t = (double)i / (n - 1);
-        u[i] = t;
-        for (int d = 0; d < D; ++d) pts[(size_t)i * D + d] = (1 - t) * start[d] + t * end[d];
-    }
-    if (sspp::interpolate(pts.data(), n, D, deg, u.data(), knots_out, ctrl0.data()) != 0)
-        return sspp::set_error(SSPP_E_INVAL, "initializePath: interpolation failed");
+    std::vector<double> ctrl0((size_t)n * D);
+    int rc;
+    if ((rc = sspp::initialize_path(start, end, n, D, deg, knots_out, ctrl0.data()))) return rc;
     hipStream_t st = (hipStream_t)sspp::shared_stream(0);
     const int64_t B = sample_count;
     const size_t nc = (size_t)B * n * D;
     Dev<double> d_ctrl, d_arc;
     Dev<uint8_t> d_f;
     Dev<sspp_best> d_b;
-    int rc;
     if ((rc = d_ctrl.reserve(nc)) || (rc = d_arc.reserve((size_t)B)) || (rc = d_f.reserve((size_t)B)) ||
         (rc = d_b.reserve(1)))
         return rc;
@@ -515,25 +453,19 @@ extern "C" int sspp_chain_plan_many_host(sspp_chain* c, int Q, const double* sta
     if (n < deg + 1)
         return sspp::set_error(SSPP_E_INVAL, "sspp_chain_plan_many_host: init_points must be >= 4 for a cubic spline");
     if (check_points < 2) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_plan_many_host: check_points must be >= 2");
-    // initializePath per query (include/sspp.h:82-97); the knot vector depends on n only
+    // initializePath per query; the knot vector depends on n only
     const size_t nd = (size_t)n * D;
     const int64_t B = sample_count;
-    std::vector<double> u((size_t)n), pts(nd), ctrl0((size_t)Q * nd);
-    for (int i = 0; i < n; ++i) u[i] = (double)i / (n - 1);
-    for (int q = 0; q < Q; ++q) {
-        for (int i = 0; i < n; ++i) {
-            const double t = u[i];
-            for (int d = 0; d < D; ++d)
-                pts[(size_t)i * D + d] = (1 - t) * starts[(size_t)q * D + d] + t * ends[(size_t)q * D + d];
-        }
-        if (sspp::interpolate(pts.data(), n, D, deg, u.data(), knots_out, ctrl0.data() + q * nd) != 0)
-            return sspp::set_error(SSPP_E_INVAL, "initializePath: interpolation failed");
-    }
+    std::vector<double> ctrl0((size_t)Q * nd);
+    int rc;
+    for (int q = 0; q < Q; ++q)
+        if ((rc = sspp::initialize_path(starts + (size_t)q * D, ends + (size_t)q * D, n, D, deg, knots_out,
+                                        ctrl0.data() + q * nd)))
+            return rc;
     const int chunk = (int)std::min<size_t>(kChainMaxQueries,
                                             std::max<size_t>(1, kChainManyCtrlBytes / (sizeof(double) * (size_t)B * nd)));
     const int qc_max = std::min(Q, chunk);
     hipStream_t st = (hipStream_t)sspp::shared_stream(0);
-    int rc;
     if ((rc = c->dm_arc.reserve((size_t)qc_max * B)) || (rc = c->dm_feas.reserve((size_t)qc_max * B)) ||
         (rc = c->hm_best.reserve((size_t)Q)) || (rc = c->hm_ctrl.reserve((size_t)Q * nd)) ||
         (arc_out && (rc = c->hm_arc.reserve((size_t)Q * B))) || (feasible_out && (rc = c->hm_feas.reserve((size_t)Q * B))))

@@ -1,6 +1,7 @@
 // sspp_chain_dev.h — what the chain's two translation units share (sspp_chain.hip: kinematics,
 // contact decisions, scoring; sspp_chain_report.hip: the contact report): the device view of the
-// tables, the LDS-backed frame accessor, the chain object and its per-shape job cache.
+// tables, the LDS-backed frame accessor, the launches' block count and the _host calls' tail, the
+// chain object and its per-shape job cache.
 #pragma once
 #include "sspp_chain.h"
 
@@ -24,6 +25,21 @@ struct LdsFrames {
 };
 
 inline size_t chain_lds(int nd) { return sizeof(double) * 7 * kChainBlock * (size_t)std::max(1, nd); }
+
+// workgroups of kChainBlock lanes for a launch over items poses
+inline int chain_blocks(int64_t items, const char* who, int* out) {
+    const int64_t nblk = (items + kChainBlock - 1) / kChainBlock;
+    if (nblk > 0x7fffffffll) return sspp::set_error(SSPP_E_INVAL, std::string(who) + ": too many poses for one launch");
+    *out = (int)nblk;
+    return SSPP_OK;
+}
+
+// the tail of a _host call: its stream is waited for also after a failure (work is queued on it, and
+// the staged input and the outputs die with the caller's frame)
+inline int chain_wait(hipStream_t st, int rc, const char* what) {
+    const int rs = sspo::hip_fail(hipStreamSynchronize(st), what);
+    return rc ? rc : rs;
+}
 
 }  // namespace sspc
 

@@ -157,13 +157,6 @@ __global__ __launch_bounds__(kChainBlock) void k_chain_first(const ChainT T, con
     if (lane == 0) first[b] = sspp_chain_first{wp, col};
 }
 
-static int report_blocks(int64_t items, const char* who, int* out) {
-    const int64_t nblk = (items + kChainBlock - 1) / kChainBlock;
-    if (nblk > 0x7fffffffll) return sspp::set_error(SSPP_E_INVAL, std::string(who) + ": too many poses for one launch");
-    *out = (int)nblk;
-    return SSPP_OK;
-}
-
 // the path forms' arguments past the chain and the batch, and the scene-less job of the shape
 static int path_job(sspp_chain* c, const char* who, const double* knots, int degree, int n, int W) {
     if (n < 1 || W < 1)
@@ -200,7 +193,7 @@ extern "C" int sspp_chain_pair_contacts(const sspp_chain* c, const double* d_q, 
     if (N == 0 || T.np == 0) return SSPP_OK;
     if (!d_q || !d_contact) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_pair_contacts: null poses / contact output");
     int nblk = 0;
-    if (int rc = report_blocks(N, "sspp_chain_pair_contacts", &nblk)) return rc;
+    if (int rc = chain_blocks(N, "sspp_chain_pair_contacts", &nblk)) return rc;
     hipLaunchKernelGGL(k_chain_pair_contacts, dim3(nblk), dim3(kChainBlock), report_lds(T.nd, T.np, d_deep != nullptr),
                        (hipStream_t)stream, T, d_q, (long long)N, d_contact, d_deep);
     return sspo::hip_fail(hipGetLastError(), "sspp_chain_pair_contacts launch");
@@ -220,7 +213,7 @@ extern "C" int sspp_chain_path_contacts(sspp_chain* c, const double* knots, int 
     if (B > 0x7fffffffll * kChainBlock / Wn)
         return sspp::set_error(SSPP_E_INVAL, "sspp_chain_path_contacts: too many poses for one launch");
     int nblk = 0;
-    if (int rc = report_blocks(B * Wn, "sspp_chain_path_contacts", &nblk)) return rc;
+    if (int rc = chain_blocks(B * Wn, "sspp_chain_path_contacts", &nblk)) return rc;
     hipLaunchKernelGGL(k_chain_path_contacts, dim3(nblk), dim3(kChainBlock), report_lds(T.nd, T.np, d_deep != nullptr),
                        (hipStream_t)stream, T, j->p, j->n, Wn, j->d_tab.p, j->d_span.p, d_ctrl, (long long)B * Wn,
                        d_contact, d_deep);
@@ -253,9 +246,7 @@ static int report_back(hipStream_t st, int rc, const Dev<uint8_t>& d_c, const De
                        uint8_t* contact, uint8_t* deep) {
     if (!rc && bytes) rc = hip_fail(hipMemcpyAsync(contact, d_c.p, bytes, hipMemcpyDeviceToHost, st), "copy contact");
     if (!rc && bytes && deep) rc = hip_fail(hipMemcpyAsync(deep, d_d.p, bytes, hipMemcpyDeviceToHost, st), "copy deep");
-    // (also after a failure: the staged input and the outputs die with the caller's frame)
-    const int rs = hip_fail(hipStreamSynchronize(st), "chain contact report");
-    return rc ? rc : rs;
+    return chain_wait(st, rc, "chain contact report");
 }
 
 extern "C" int sspp_chain_pair_contacts_host(const sspp_chain* c, const double* q, int64_t N, uint8_t* contact,
@@ -309,6 +300,5 @@ extern "C" int sspp_chain_first_contacts_host(sspp_chain* c, const double* knots
     rc = hip_fail(hipMemcpyAsync(d_ctrl.p, ctrl, sizeof(double) * nc, hipMemcpyHostToDevice, st), "copy splines");
     if (!rc) rc = sspp_chain_first_contacts(c, knots, degree, d_ctrl.p, B, n, W, d_f.p, st);
     if (!rc) rc = hip_fail(hipMemcpyAsync(first, d_f.p, sizeof(sspp_chain_first) * (size_t)B, hipMemcpyDeviceToHost, st), "copy first contacts");
-    const int rs = hip_fail(hipStreamSynchronize(st), "sspp_chain_first_contacts_host");
-    return rc ? rc : rs;
+    return chain_wait(st, rc, "sspp_chain_first_contacts_host");
 }

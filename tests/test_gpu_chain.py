@@ -211,6 +211,40 @@ def test_score_ctrl_single_contact_at_the_ends(S, exe, tmp, Wc):
     assert best[1] == 0  # two equal arcs: the lowest id
 
 
+@pytest.mark.parametrize("B", [255, 256, 257, 513])
+def test_score_ctrl_argmin_across_the_reduction(S, exe, tmp, B):
+    """the single-query argmin at batches around and past its 256 threads (a thread then holds more
+    than one candidate, and the tree reduces every slot), with ids past 2^32.  The crafted arm's
+    `free` spline is feasible and `first` is not, so feasibility is placed candidate by candidate:
+    (a) only the last candidate feasible; (b) two feasible candidates with identical splines 256
+    apart, in one thread's stride: the lower id wins (batches of at least 257; a smaller one has
+    no such pair); (c) none feasible: the record is {+inf, -1, 0}."""
+    world, r = TH.crafted_world()
+    xml = H.write_xml(tmp, "crafted", W.mjcf(world))
+    ch = S.Chain(S.Model(xml, joints=True), 3, count_static=False)
+    n, degree, Wc, first_id = 6, 3, 8, 2**40 + 5
+    up, down = np.array([0.0, 0.1, 0.0]), np.array([0.0, 0.47, 0.0])
+    knots, free = linear_ctrl(S, up, up, n, degree)
+    first = free.copy()
+    first[0] = down
+    pair_feas, _ = host_feasible(S, exe, tmp, xml, 3, knots, degree, np.stack([free, first]), Wc, "argmin")
+    assert pair_feas.tolist() == [True, False]
+    cases = {"a": [B - 1], "c": []}
+    if B >= 257:
+        k = (B - 257) // 2
+        cases["b"] = [k, k + 256]
+    for name, feasible_at in cases.items():
+        want_feas = np.zeros(B, bool)
+        want_feas[feasible_at] = True
+        ctrl = np.where(want_feas[:, None, None], free[None], first[None])
+        arc, feas, best = run_score(S, ch, knots, degree, ctrl, Wc, first_id=first_id)
+        check_scores(arc, feas, best, want_feas, job_arcs(S, knots, degree, ctrl, Wc), first_id)
+        if name == "c":
+            assert best[2] == 0 and best[1] == -1 and np.isposinf(best[0])
+        else:
+            assert best[1] == first_id + feasible_at[0]
+
+
 # ------------------------------------------------------------------ sample_score
 def test_sample_score(S, exe, tmp, arms):
     import torch
