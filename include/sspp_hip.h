@@ -335,7 +335,7 @@ int sspp_path_contacts_host(const sspp_scene* s, const double* knots, int degree
  * The device calls are asynchronous on `stream`; N = 0 or B = 0 is SSPP_OK without a launch.  The
  * scoring calls keep a scene-less job per spline shape (knots, n, W): the first call of a shape or
  * of a larger B allocates, later ones do not.  Out of scope for a chain: TaskSpacePlanner / CES,
- * re-posing, joint limits. */
+ * joint limits.  Re-posing: "worlds for arms" below. */
 #define SSPP_JNT_FREE 0
 #define SSPP_JNT_SLIDE 2
 #define SSPP_JNT_HINGE 3
@@ -431,6 +431,63 @@ int sspp_chain_plan_many_host(sspp_chain* c, int Q, const double* starts /* [Q][
                               double* knots_out /* [init_points + 4] */, sspp_best* best_out /* [Q] */,
                               double* best_ctrl_out /* [Q][init_points][dof] */, int64_t* n_feasible /* [Q] */,
                               double* arc_out /* nullable [Q][sample_count] */, uint8_t* feasible_out /* nullable */);
+
+/* ---- worlds for arms (DESIGN.md §5 "Worlds for arms") ----
+ * A chain's world is what its pose rule does not drive: a full qpos [nq] in the model's layout (7 per
+ * free joint, 1 per hinge / slide) and the bodies' pos / quat.  At creation it is the model's
+ * (qpos = qpos0).  The pose rule is q[0:dof] -> qpos[0:dof], the rest from the world: a hinge or slide
+ * at an address >= dof turns / moves by world[adr] - qpos0[adr] (qpos0 stays the joint's zero), a free
+ * body at an address >= dof sits at its 7 world values, and one that dof cuts takes its components at
+ * or past dof from the world.  World entries below dof are stored and returned, never read.
+ *   sspp_chain_set_qpos       the whole qpos.  Free-joint quaternions are normalised as the loader
+ *                             normalises them
+ *   sspp_chain_set_body_pose  one body: a free-joint body -> its 7 qpos; any other body (static, or
+ *                             inside the driven chain: an arm's base, a tool offset) -> its pos / quat
+ *                             relative to its parent, and its children follow
+ *   sspp_chain_get_qpos       the current world's qpos
+ *   sspp_chain_epoch          0 at creation, +1 per successful update
+ * An update runs the builder that created the chain on the chain's own copy of the model data (the
+ * sspp_model is never touched) and adopts the result: the chain then equals, table byte for table
+ * byte, one created from a model holding the new values.  The pair filter does not look at poses, so
+ * the pair table, every table's length and the driven set stay; static geoms' poses, a driven body's
+ * static-parent pose, frozen values, the static pairs' counts and static_contacts change.  The calls
+ * are host-synchronous with sspp_scene_set_qpos's lifetime rules (the device is drained; no launch
+ * that reads the chain may be queued concurrently); the device tables, the per-shape job, the
+ * candidate buffers and the pinned memory keep their allocations: an update allocates nothing.  A
+ * wrong nq, a non-finite value, a zero quaternion or a body outside [1, nbody) is SSPP_E_INVAL and
+ * leaves the chain as it was.  Every chain call afterwards reads the new world.
+ *
+ * A world per query: sspp_chain_sample_score_worlds / sspp_chain_plan_many_worlds_host are the query
+ * calls above with one more argument, worlds (host [Q][nq]).  Query q is scored in the chain's
+ * current world with its qpos replaced by worlds[q] (body poses are the chain's: an obstacle that
+ * differs per query carries a free joint); row q of every output is, byte for byte, what
+ * sspp_chain_sample_score (sspp_chain_plan_host) writes for query q alone after
+ * sspp_chain_set_qpos(worlds[q]).  With count_static, a query whose world has static contacts has
+ * every candidate infeasible; the others are not affected.  The chain's own world, its epoch and the
+ * plain calls' results stay.  The tables of the Q worlds are built on the host, staged in pinned
+ * memory of the chain's and copied, stream-ordered, into device arrays [Q][..] that grow only; the
+ * staging is rewritten only after the event behind the previous copies out of it (copies only, never
+ * a kernel).  A bad world anywhere in the set is SSPP_E_INVAL with nothing staged or launched. */
+int sspp_chain_set_qpos(sspp_chain* c, const double* qpos, int nq);
+int sspp_chain_get_qpos(const sspp_chain* c, double* qpos_out, int nq);
+int sspp_chain_set_body_pose(sspp_chain* c, int body, const double pos[3], const double quat[4]);
+int sspp_chain_epoch(const sspp_chain* c, int64_t* epoch);
+int sspp_chain_sample_score_worlds(sspp_chain* c, const double* knots, int degree, int Q,
+                                   const double* init_ctrl /* host [Q][n][dof] */, int n, int W,
+                                   const double* sigma /* [Q] */, const double* limits /* [Q][dof] */,
+                                   const uint64_t* seed /* [Q] */, int64_t first_id, int64_t B,
+                                   double* d_arc /* [Q][B] */, uint8_t* d_feasible /* [Q][B] */,
+                                   double* d_ctrl_out /* nullable [Q][B][n][dof] */,
+                                   sspp_best* d_best /* nullable [Q] */,
+                                   double* d_best_ctrl /* nullable [Q][n][dof] */, void* stream,
+                                   const double* worlds /* host [Q][nq] */);
+int sspp_chain_plan_many_worlds_host(sspp_chain* c, int Q, const double* starts /* [Q][dof] */, const double* ends,
+                                     double sigma, const double* limits /* [dof] */, int sample_count,
+                                     int check_points, int init_points, const uint64_t* seeds /* [Q] */,
+                                     int64_t first_id, double* knots_out /* [init_points + 4] */,
+                                     sspp_best* best_out /* [Q] */, double* best_ctrl_out /* [Q][init_points][dof] */,
+                                     int64_t* n_feasible /* [Q] */, double* arc_out /* nullable [Q][sample_count] */,
+                                     uint8_t* feasible_out /* nullable */, const double* worlds /* [Q][nq] */);
 
 /* ---- contact report for arms (DESIGN.md §5 "Contact report for arms") ----
  * Which pairs of a chain a pose or a path touches.  Columns: the chain's pair table in

@@ -167,6 +167,15 @@ SIGNATURES = {
                                                   _vp, _vp, _vp, _vp, _vp, _vp]),
     "sspp_chain_plan_many_host": (C.c_int, [_vp, _i, _d, _d, C.c_double, _d, _i, _i, _i, C.POINTER(C.c_uint64), _i64,
                                             _d, C.POINTER(Best), _d, C.POINTER(_i64), _d, C.POINTER(C.c_uint8)]),
+    "sspp_chain_set_qpos": (C.c_int, [_vp, _d, _i]),
+    "sspp_chain_get_qpos": (C.c_int, [_vp, _d, _i]),
+    "sspp_chain_set_body_pose": (C.c_int, [_vp, _i, _d, _d]),
+    "sspp_chain_epoch": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "sspp_chain_sample_score_worlds": (C.c_int, [_vp, _d, _i, _i, _d, _i, _i, _d, _d, C.POINTER(C.c_uint64), _i64, _i64,
+                                                 _vp, _vp, _vp, _vp, _vp, _vp, _d]),
+    "sspp_chain_plan_many_worlds_host": (C.c_int, [_vp, _i, _d, _d, C.c_double, _d, _i, _i, _i, C.POINTER(C.c_uint64),
+                                                   _i64, _d, C.POINTER(Best), _d, C.POINTER(_i64), _d,
+                                                   C.POINTER(C.c_uint8), _d]),
     "sspp_chain_static_pairs": (C.c_int, [_vp, C.POINTER(PairInfo), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), _i,
                                           C.POINTER(C.c_int)]),
     "sspp_chain_pair_contacts": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp]),

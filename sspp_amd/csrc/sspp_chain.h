@@ -16,6 +16,11 @@
 // and puts xpos at anchor - R(xquat) jnt_pos.  Finally xquat is normalised.  Geom poses from body
 // poses as sspb::host_fk forms them.
 //
+// Worlds (DESIGN.md §5 "Worlds for arms"): what the pose rule does not drive comes from a world, a
+// full qpos [nq] beside the model's body poses.  qpos0 stays every joint's zero; a frozen joint's
+// value (CJoint::qf) and a frozen free body's (CBody::q0, components at or past D) are the world's.
+// chain_build takes the world, so creation, re-posing and a query's own world are one builder.
+//
 // Frames are read and written through an accessor (get / set of (body slot, component 0..6: pos,
 // quat)), and the pose's values through a functor of the qpos address, so that a kernel can keep its
 // lanes' frames in LDS [slot][component][lane] and evaluate a spline's coordinate when a joint asks
@@ -68,12 +73,13 @@ struct CBody {
     int32_t jnt0, njnt;  // its hinge / slide joints in the CJoint table
     double pos[3], quat[4];    // relative to the parent (mjModel.body_pos / body_quat)
     double ppos[3], pquat[4];  // a static parent's world pose
-    double q0[7];              // a free body's qpos0
+    double q0[7];              // a free body's frozen values: the world's at addresses >= D (qpos0 below)
 };
 struct CJoint {
     int32_t type;  // 2 slide, 3 hinge
-    int32_t adr;   // qpos address below D, -1: frozen at qpos0
-    double axis[3], pos[3], q0;
+    int32_t adr;   // qpos address below D, -1: frozen at qf
+    double axis[3], pos[3], q0;  // q0: the joint's zero (qpos0)
+    double qf;     // the world's value of a frozen joint (q0 for a driven one: never read)
 };
 // every geom of the model, model order
 struct CGeom {
@@ -147,7 +153,7 @@ SSPP_HD void chain_fk(BP bodies, JP joints, int nd, int D, const QV& qv, const F
             for (int j = j0; j < j1; ++j) {
                 const int adr = joints[j].adr;
                 const double q0 = joints[j].q0;
-                const double a = (adr >= 0 ? qv(adr) : q0) - q0;
+                const double a = (adr >= 0 ? qv(adr) : (double)joints[j].qf) - q0;
                 double ax[3], jp[3], xa[3], anchor[3];
 #pragma unroll
                 for (int k = 0; k < 3; ++k) { ax[k] = joints[j].axis[k]; jp[k] = joints[j].pos[k]; }
@@ -269,9 +275,11 @@ struct ChainTables {
 };
 
 // body and joint records of the bodies with in[b] != 0 (closed under descendants), joints with a
-// qpos address at or past D frozen; wframe: world frames [nbody][7] of the bodies outside the set
-inline void chain_records(const sspp_model& m, int D, const std::vector<int>& in, const std::vector<double>& wframe,
-                          std::vector<CBody>& bodies, std::vector<CJoint>& joints, std::vector<int>& slot_of) {
+// qpos address at or past D frozen at world's values (world: qpos [nq], chain_build's: qpos0 below
+// its D); wframe: world frames [nbody][7] of the bodies outside the set
+inline void chain_records(const sspp_model& m, int D, const double* world, const std::vector<int>& in,
+                          const std::vector<double>& wframe, std::vector<CBody>& bodies, std::vector<CJoint>& joints,
+                          std::vector<int>& slot_of) {
     const int nb = m.nbody();
     slot_of.assign(nb, -1);
     for (int b = 1; b < nb; ++b) {
@@ -288,7 +296,7 @@ inline void chain_records(const sspp_model& m, int D, const std::vector<int>& in
             for (int k = 0; k < 4; ++k) B.pquat[k] = wframe[7 * pa + 3 + k];
         }
         if (B.free_adr >= 0) {
-            for (int k = 0; k < 7; ++k) B.q0[k] = m.qpos0[B.free_adr + k];
+            for (int k = 0; k < 7; ++k) B.q0[k] = world[B.free_adr + k];
         } else {
             B.jnt0 = (int)joints.size();
             for (int j = m.body_jnt_adr[b]; j < m.body_jnt_adr[b] + m.body_jnt_num[b]; ++j) {
@@ -297,6 +305,7 @@ inline void chain_records(const sspp_model& m, int D, const std::vector<int>& in
                 J.adr = m.jnt_qpos_adr[j] < D ? m.jnt_qpos_adr[j] : -1;
                 for (int k = 0; k < 3; ++k) { J.axis[k] = m.jnt_axis[3 * j + k]; J.pos[k] = m.jnt_pos[3 * j + k]; }
                 J.q0 = m.qpos0[m.jnt_qpos_adr[j]];
+                J.qf = world[m.jnt_qpos_adr[j]];
                 joints.push_back(J);
             }
             B.njnt = (int)joints.size() - B.jnt0;
@@ -306,10 +315,63 @@ inline void chain_records(const sspp_model& m, int D, const std::vector<int>& in
     }
 }
 
-// The tables of model m for the pose rule q[0:D] -> qpos[0:D].  SSPP_E_INVAL for D out of range,
+// n finite values and, where given, a quaternion that is not zero (sspb::pose_values_ok's test)
+inline bool world_values_ok(const double* v, int n, const double* quat) {
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return !quat || quat[0] != 0.0 || quat[1] != 0.0 || quat[2] != 0.0 || quat[3] != 0.0;
+}
+
+// A world's qpos, validated and normalised as the loader does, into out [nq]: SSPP_E_INVAL (message
+// set, out untouched) for a wrong nq, a non-finite value or a free joint's zero quaternion.
+inline int chain_world_qpos(const sspp_model& m, const double* qpos, int nq, const char* who, std::vector<double>& out) {
+    if (!qpos) return sspp::set_error(SSPP_E_INVAL, std::string(who) + ": null qpos");
+    if (nq != (int)m.qpos0.size())
+        return sspp::set_error(SSPP_E_INVAL, std::string(who) + ": nq = " + std::to_string(nq) + ", the model has " +
+                                                 std::to_string(m.qpos0.size()));
+    for (int j = 0; j < m.njnt(); ++j) {
+        const int a = m.jnt_qpos_adr[j], w = m.jnt_type[j] == 0 ? 7 : 1;
+        if (!world_values_ok(qpos + a, w, w == 7 ? qpos + a + 3 : nullptr))
+            return sspp::set_error(SSPP_E_INVAL, std::string(who) + ": non-finite value or zero quaternion at qpos[" +
+                                                     std::to_string(a) + ":" + std::to_string(a + w) + "]");
+    }
+    out.assign(qpos, qpos + nq);
+    for (int j = 0; j < m.njnt(); ++j)
+        if (m.jnt_type[j] == 0) sspp::loader_normq(&out[m.jnt_qpos_adr[j] + 3]);
+    return SSPP_OK;
+}
+
+// One body's new pose into model data m and world (sspp_chain_set_body_pose): a free-joint body's 7
+// world values (and, as the loader leaves them, its body_pos / body_quat); any other body's pose
+// relative to its parent.  SSPP_E_INVAL (message set) leaves both untouched.
+inline int chain_world_body_pose(sspp_model& m, std::vector<double>& world, int body, const double* pos, const double* quat) {
+    if (!pos || !quat) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_set_body_pose: null pos / quat");
+    if (body < 1 || body >= m.nbody())
+        return sspp::set_error(SSPP_E_INVAL, "sspp_chain_set_body_pose: body id " + std::to_string(body) +
+                                                 " out of range [1, " + std::to_string(m.nbody()) + ")");
+    if (!world_values_ok(pos, 3, nullptr) || !world_values_ok(quat, 4, quat))
+        return sspp::set_error(SSPP_E_INVAL, "sspp_chain_set_body_pose: non-finite value or zero quaternion");
+    double q[4] = {quat[0], quat[1], quat[2], quat[3]};
+    sspp::loader_normq(q);
+    for (int k = 0; k < 3; ++k) m.body_pos[3 * body + k] = pos[k];
+    for (int k = 0; k < 4; ++k) m.body_quat[4 * body + k] = q[k];
+    if (m.body_jnt_type[body] == 0) {
+        const int a = m.body_qpos_adr[body];
+        for (int k = 0; k < 3; ++k) world[a + k] = pos[k];
+        for (int k = 0; k < 4; ++k) world[a + 3 + k] = q[k];
+    }
+    return SSPP_OK;
+}
+
+// The tables of model m for the pose rule q[0:D] -> qpos[0:D], the rest from world (qpos [nq],
+// validated: chain_world_qpos; null: the model's own, qpos0).  SSPP_E_INVAL for D out of range,
 // SSPP_E_UNSUPPORTED past a limit or for a pair the narrowphase does not cover (message set).
-inline int chain_build(const sspp_model& m, int D, ChainTables& out) {
+inline int chain_build(const sspp_model& m, int D, ChainTables& out, const double* world = nullptr) {
     out = ChainTables();
+    // entries below D are the pose's: never read, so the tables hold qpos0 there in every world
+    std::vector<double> held(m.qpos0);
+    for (size_t a = (size_t)std::max(D, 0); world && a < held.size(); ++a) held[a] = world[a];
+    world = held.data();
     const int nb = m.nbody(), ng = m.ngeom(), nq = (int)m.qpos0.size();
     if (D < 1) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_create: dof must be >= 1");
     if (D > nq)
@@ -319,14 +381,14 @@ inline int chain_build(const sspp_model& m, int D, ChainTables& out) {
         return sspp::set_error(SSPP_E_UNSUPPORTED, "sspp_chain_create: dof = " + std::to_string(D) +
                                                        " exceeds the limit of " + std::to_string(kMaxDof));
     out.D = D;
-    // world frames of every body at qpos0: the same routine over all bodies with every joint frozen
+    // world frames of every body in the world: the same routine over all bodies with every joint frozen
     std::vector<double> wframe((size_t)7 * nb, 0.0);
     wframe[3] = 1.0;
     {
         std::vector<int> all(nb, 1), slot_of;
         std::vector<CBody> bodies;
         std::vector<CJoint> joints;
-        chain_records(m, 0, all, std::vector<double>(), bodies, joints, slot_of);
+        chain_records(m, 0, world, all, std::vector<double>(), bodies, joints, slot_of);
         std::vector<double> f((size_t)7 * std::max(1, nb - 1));
         chain_fk(bodies.data(), joints.data(), (int)bodies.size(), 0, [](int) { return 0.0; }, ArrayFrames{f.data()});
         for (int b = 1; b < nb; ++b)
@@ -341,7 +403,7 @@ inline int chain_build(const sspp_model& m, int D, ChainTables& out) {
         weld[b] = m.body_jnt_num[b] > 0 ? b : weld[m.body_parent[b]];
     }
     std::vector<int> slot_of;
-    chain_records(m, D, driven, wframe, out.bodies, out.joints, slot_of);
+    chain_records(m, D, world, driven, wframe, out.bodies, out.joints, slot_of);
     if ((int)out.bodies.size() > kMaxBodies)
         return sspp::set_error(SSPP_E_UNSUPPORTED, "sspp_chain_create: " + std::to_string(out.bodies.size()) +
                                                        " driven bodies exceed the limit of " +
@@ -414,6 +476,30 @@ inline int chain_build(const sspp_model& m, int D, ChainTables& out) {
     if ((int)out.pairs.size() > kMaxPairs)
         return sspp::set_error(SSPP_E_UNSUPPORTED, "sspp_chain_create: " + std::to_string(out.pairs.size()) +
                                                        " pairs exceed the limit of " + std::to_string(kMaxPairs));
+    return SSPP_OK;
+}
+
+// what a world cannot change (the pair filter does not look at poses): the driven set, every
+// table's length, the pair table and the bounding radii
+inline bool chain_same_shape(const ChainTables& a, const ChainTables& b) {
+    if (a.D != b.D || a.bodies.size() != b.bodies.size() || a.joints.size() != b.joints.size() ||
+        a.geoms.size() != b.geoms.size() || a.pairs.size() != b.pairs.size() || a.statics.size() != b.statics.size() ||
+        a.slot_body != b.slot_body || a.n_moving_geoms != b.n_moving_geoms || a.n_static_pairs != b.n_static_pairs)
+        return false;
+    for (size_t k = 0; k < a.pairs.size(); ++k)
+        if (a.pairs[k].a != b.pairs[k].a || a.pairs[k].b != b.pairs[k].b || a.pairs[k].margin != b.pairs[k].margin)
+            return false;
+    for (size_t g = 0; g < a.geoms.size(); ++g)
+        if (a.geoms[g].slot != b.geoms[g].slot || a.geoms[g].rbound != b.geoms[g].rbound) return false;
+    return true;
+}
+
+// An update's host half: the tables of (trial, world) by the builder that made `cur`, checked to
+// have cur's shape.  The caller adopts trial, world and out; a failure (message set) leaves all as
+// they were.
+inline int chain_update(const ChainTables& cur, const sspp_model& trial, const std::vector<double>& world, ChainTables& out) {
+    if (int rc = chain_build(trial, cur.D, out, world.data())) return rc;
+    if (!chain_same_shape(cur, out)) return sspp::set_error(SSPP_E_INVAL, "sspp_chain: a world changed the shape of the tables");
     return SSPP_OK;
 }
 

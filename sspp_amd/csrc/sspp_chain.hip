@@ -62,19 +62,32 @@ __global__ __launch_bounds__(kChainBlock) void k_chain_contacts(const ChainT T, 
 // One wave per candidate b: waypoint i = pass * 64 + lane at u = i / W, from the job's basis rows
 // (tab: P + 1 values per waypoint, span: its knot span).  Writes feasible[b], and +inf over an
 // infeasible candidate's arc length.
-__global__ __launch_bounds__(kChainBlock) void k_chain_feas(const ChainT T, const int static_block, const int P,
-                                                             const int n, const int W,
-                                                             const double* __restrict__ tab,
-                                                             const int* __restrict__ span,
-                                                             const double* __restrict__ ctrl,
-                                                             double* __restrict__ arc,
-                                                             uint8_t* __restrict__ feasible) {
-    extern __shared__ double s_fr[];
+// WORLDS (a worlds launch, DESIGN.md §5 "Worlds for arms"): candidate b belongs to query b / B, which
+// is wave-uniform; T's body, joint and geom tables are [Q][nd], [Q][nj], [Q][ng] and their bases are
+// offset by the query (still scalar loads from the constant address space; the pair table is
+// shared), and the static block is bit b / B of static_mask.  A compile-time flag: the plain
+// kernel's code is what it was.
+template <bool WORLDS>
+__device__ __forceinline__ void chain_feas(const ChainT& T, const unsigned long long static_mask, const int nj,
+                                           const unsigned B, const int P, const int n, const int W,
+                                           const double* __restrict__ tab, const int* __restrict__ span,
+                                           const double* __restrict__ ctrl, double* __restrict__ arc,
+                                           uint8_t* __restrict__ feasible, double* s_fr) {
     const long long b = blockIdx.x;
     const int lane = threadIdx.x;
     const LdsFrames fr{s_fr + lane};
     const int D = T.D;
-    bool blocked = static_block != 0;
+    cbody_t bodies = (cbody_t)T.bodies;
+    cjoint_t joints = (cjoint_t)T.joints;
+    ccgeom_t geoms = (ccgeom_t)T.geoms;
+    bool blocked = static_mask != 0;
+    if (WORLDS) {
+        const unsigned qi = blockIdx.x / B;  // (< 64: the launch has at most 64 queries)
+        bodies += (size_t)qi * T.nd;
+        joints += (size_t)qi * nj;
+        geoms += (size_t)qi * T.ng;
+        blocked = ((static_mask >> qi) & 1ull) != 0;
+    }
     for (int base = 0; base <= W && !blocked; base += kChainBlock) {
         const int i = base + lane;
         int h = 0;
@@ -92,8 +105,8 @@ __global__ __launch_bounds__(kChainBlock) void k_chain_feas(const ChainT T, cons
                     if (r <= P) acc = fma(Nr[r], c0[r * D + adr], acc);
                 return acc;
             };
-            chain_fk((cbody_t)T.bodies, (cjoint_t)T.joints, T.nd, D, qv, fr);
-            h = chain_contact((ccgeom_t)T.geoms, (ccpair_t)T.pairs, T.np, fr);
+            chain_fk(bodies, joints, T.nd, D, qv, fr);
+            h = chain_contact(geoms, (ccpair_t)T.pairs, T.np, fr);
         }
         blocked = __any(h) != 0;  // wave-uniform: every lane leaves the loop together
     }
@@ -101,6 +114,30 @@ __global__ __launch_bounds__(kChainBlock) void k_chain_feas(const ChainT T, cons
         feasible[b] = blocked ? 0 : 1;
         if (blocked) arc[b] = INFINITY;
     }
+}
+
+__global__ __launch_bounds__(kChainBlock) void k_chain_feas(const ChainT T, const int static_block, const int P,
+                                                             const int n, const int W,
+                                                             const double* __restrict__ tab,
+                                                             const int* __restrict__ span,
+                                                             const double* __restrict__ ctrl,
+                                                             double* __restrict__ arc,
+                                                             uint8_t* __restrict__ feasible) {
+    extern __shared__ double s_fr[];
+    chain_feas<false>(T, static_block != 0, 0, 1, P, n, W, tab, span, ctrl, arc, feasible, s_fr);
+}
+
+// the worlds form: a batch of Q * B candidates, query q's in [q B, (q + 1) B); nj: joint records per world
+__global__ __launch_bounds__(kChainBlock) void k_chain_feas_w(const ChainT T, const unsigned long long static_mask,
+                                                               const int nj, const unsigned B, const int P,
+                                                               const int n, const int W,
+                                                               const double* __restrict__ tab,
+                                                               const int* __restrict__ span,
+                                                               const double* __restrict__ ctrl,
+                                                               double* __restrict__ arc,
+                                                               uint8_t* __restrict__ feasible) {
+    extern __shared__ double s_fr[];
+    chain_feas<true>(T, static_mask, nj, B, P, n, W, tab, span, ctrl, arc, feasible, s_fr);
 }
 
 // findBestPath per row q of arc / feasible [Q][B], one workgroup each: the (arc, id) minimum over
@@ -175,11 +212,68 @@ extern "C" int sspp_chain_create(const sspp_model* m, int dof, int count_static,
         delete c;
         return rc;
     }
+    c->model = *m;  // (the updates edit this copy: the caller's model is never touched)
+    c->world = m->qpos0;
     *out = c;
     return SSPP_OK;
 }
 
 extern "C" void sspp_chain_free(sspp_chain* c) { delete c; }
+
+// ---------------------------------------------------------------- worlds (DESIGN.md §5 "Worlds for arms")
+// The chain to the world of (trial, world): a copy of its model data with new body_pos / body_quat,
+// and a validated qpos.  The builder that created the chain runs first, so nothing is touched on a
+// failure; then the device is drained and the tables are copied into the allocations they have.
+static int chain_repose(sspp_chain* c, sspp_model&& trial, std::vector<double>&& world) {
+    ChainTables t;
+    if (int rc = chain_update(c->t, trial, world, t)) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    if (!t.bodies.empty())
+        HIPCHK(hipMemcpy(c->d_bodies.p, t.bodies.data(), sizeof(CBody) * t.bodies.size(), hipMemcpyHostToDevice));
+    if (!t.joints.empty())
+        HIPCHK(hipMemcpy(c->d_joints.p, t.joints.data(), sizeof(CJoint) * t.joints.size(), hipMemcpyHostToDevice));
+    if (!t.geoms.empty())
+        HIPCHK(hipMemcpy(c->d_geoms.p, t.geoms.data(), sizeof(CGeom) * t.geoms.size(), hipMemcpyHostToDevice));
+    c->t = std::move(t);
+    c->model = std::move(trial);
+    c->world = std::move(world);
+    ++c->epoch;
+    return SSPP_OK;
+}
+
+extern "C" int sspp_chain_set_qpos(sspp_chain* c, const double* qpos, int nq) {
+    sspp::clear_error();
+    if (!c) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_set_qpos: null chain");
+    std::vector<double> world;
+    if (int rc = chain_world_qpos(c->model, qpos, nq, "sspp_chain_set_qpos", world)) return rc;
+    return chain_repose(c, sspp_model(c->model), std::move(world));
+}
+
+extern "C" int sspp_chain_set_body_pose(sspp_chain* c, int body, const double pos[3], const double quat[4]) {
+    sspp::clear_error();
+    if (!c) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_set_body_pose: null chain");
+    sspp_model trial(c->model);
+    std::vector<double> world(c->world);
+    if (int rc = chain_world_body_pose(trial, world, body, pos, quat)) return rc;
+    return chain_repose(c, std::move(trial), std::move(world));
+}
+
+extern "C" int sspp_chain_get_qpos(const sspp_chain* c, double* qpos_out, int nq) {
+    sspp::clear_error();
+    if (!c || !qpos_out) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_get_qpos: null argument");
+    if (nq != (int)c->world.size())
+        return sspp::set_error(SSPP_E_INVAL, "sspp_chain_get_qpos: nq = " + std::to_string(nq) + ", the model has " +
+                                                 std::to_string(c->world.size()));
+    if (nq) std::memcpy(qpos_out, c->world.data(), sizeof(double) * nq);
+    return SSPP_OK;
+}
+
+extern "C" int sspp_chain_epoch(const sspp_chain* c, int64_t* epoch) {
+    sspp::clear_error();
+    if (!c || !epoch) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_epoch: null argument");
+    *epoch = c->epoch;
+    return SSPP_OK;
+}
 
 extern "C" int sspp_chain_get_info(const sspp_chain* c, sspp_chain_info* out) {
     if (!c || !out) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_get_info: null argument");
@@ -268,16 +362,84 @@ int sspc::chain_job(sspp_chain* c, const double* knots, int degree, int n, int W
     return SSPP_OK;
 }
 
+// the device tables of a worlds launch's Q worlds and the queries' static blocks (bit q: query q)
+struct WorldTables {
+    const CBody* bodies;
+    const CJoint* joints;
+    const CGeom* geoms;
+    int nj;
+    unsigned long long static_mask;
+};
+
+// The tables of Q worlds (the chain's current world with its qpos replaced by worlds[q], host
+// [Q][nq]) onto the device, stream-ordered.  Every world is validated and built first: a failure
+// stages nothing.  The pinned staging and the device arrays are allocated once, for
+// kChainMaxQueries worlds; the staging is rewritten after the event behind the previous set's copies.
+static int chain_stage_worlds(sspp_chain* c, const char* who, int Q, const double* worlds, hipStream_t st,
+                              WorldTables* out) {
+    const int nq = (int)c->world.size();
+    const size_t nd = c->t.bodies.size(), nj = c->t.joints.size(), ng = c->t.geoms.size();
+    std::vector<CBody> hb;
+    std::vector<CJoint> hj;
+    std::vector<CGeom> hg;
+    std::vector<double> w;
+    ChainTables t;
+    unsigned long long mask = 0;
+    int rc;
+    for (int q = 0; q < Q; ++q) {
+        if ((rc = chain_world_qpos(c->model, worlds + (size_t)q * nq, nq, who, w)) ||
+            (rc = chain_update(c->t, c->model, w, t)))
+            return sspp::set_error(rc, "world " + std::to_string(q) + ": " + sspp_last_error());
+        hb.insert(hb.end(), t.bodies.begin(), t.bodies.end());
+        hj.insert(hj.end(), t.joints.begin(), t.joints.end());
+        hg.insert(hg.end(), t.geoms.begin(), t.geoms.end());
+        if (c->count_static && t.static_contacts > 0) mask |= 1ull << q;
+    }
+    const size_t cap = kChainMaxQueries;
+    const auto up16 = [](size_t x) { return (x + 15) / 16 * 16; };
+    const size_t oj = up16(sizeof(CBody) * cap * nd), og = oj + up16(sizeof(CJoint) * cap * nj);
+    const size_t total = og + up16(sizeof(CGeom) * cap * ng);
+    if ((rc = c->wst.wait())) return rc;
+    if (!c->dw_bodies.p && !c->dw_joints.p && !c->dw_geoms.p) {  // the first worlds launch of this chain
+        if ((rc = c->dw_bodies.reserve(cap * nd)) || (rc = c->dw_joints.reserve(cap * nj)) ||
+            (rc = c->dw_geoms.reserve(cap * ng)) || (rc = c->wst.reserve(std::max<size_t>(total, 16))))
+            return rc;
+    }
+    unsigned char* hp = c->wst.buf.p;
+    if (nd) {
+        std::memcpy(hp, hb.data(), sizeof(CBody) * hb.size());
+        HIPCHK(hipMemcpyAsync(c->dw_bodies.p, hp, sizeof(CBody) * hb.size(), hipMemcpyHostToDevice, st));
+    }
+    if (nj) {
+        std::memcpy(hp + oj, hj.data(), sizeof(CJoint) * hj.size());
+        HIPCHK(hipMemcpyAsync(c->dw_joints.p, hp + oj, sizeof(CJoint) * hj.size(), hipMemcpyHostToDevice, st));
+    }
+    if (ng) {
+        std::memcpy(hp + og, hg.data(), sizeof(CGeom) * hg.size());
+        HIPCHK(hipMemcpyAsync(c->dw_geoms.p, hp + og, sizeof(CGeom) * hg.size(), hipMemcpyHostToDevice, st));
+    }
+    if ((rc = c->wst.record(st))) return rc;
+    *out = WorldTables{c->dw_bodies.p, c->dw_joints.p, c->dw_geoms.p, (int)nj, mask};
+    return SSPP_OK;
+}
+
 // feasibility of the Q * B candidates in d_ctrl ([Q][B][n][D]) over the job's arcs, then the argmin
-// per row of B and, with d_best_ctrl, the winners' rows (many: a query launch, in a failure's message)
+// per row of B and, with d_best_ctrl, the winners' rows (many: a query launch, in a failure's
+// message; wt: a worlds launch's tables, query q's candidates in world q)
 static int chain_finish(sspp_chain* c, const double* d_ctrl, int64_t first_id, int Q, int64_t B, double* d_arc,
-                        uint8_t* d_feasible, sspp_best* d_best, double* d_best_ctrl, bool many, hipStream_t st) {
+                        uint8_t* d_feasible, sspp_best* d_best, double* d_best_ctrl, bool many, hipStream_t st,
+                        const WorldTables* wt = nullptr) {
     if (B > 0x7fffffffll)  // (a query launch has checked Q * B)
         return sspp::set_error(SSPP_E_INVAL, "sspp_chain: too many candidates for one launch");
-    const ChainT T = c->view();
+    ChainT T = c->view();
     const sspp_job* j = c->job;
-    hipLaunchKernelGGL(k_chain_feas, dim3((int)(Q * B)), dim3(kChainBlock), chain_lds(T.nd), st, T, c->static_block(),
-                       j->p, j->n, j->W, j->d_tab.p, j->d_span.p, d_ctrl, d_arc, d_feasible);
+    if (wt) {
+        T.bodies = wt->bodies; T.joints = wt->joints; T.geoms = wt->geoms;
+        hipLaunchKernelGGL(k_chain_feas_w, dim3((int)(Q * B)), dim3(kChainBlock), chain_lds(T.nd), st, T, wt->static_mask,
+                           wt->nj, (unsigned)B, j->p, j->n, j->W, j->d_tab.p, j->d_span.p, d_ctrl, d_arc, d_feasible);
+    } else
+        hipLaunchKernelGGL(k_chain_feas, dim3((int)(Q * B)), dim3(kChainBlock), chain_lds(T.nd), st, T, c->static_block(),
+                           j->p, j->n, j->W, j->d_tab.p, j->d_span.p, d_ctrl, d_arc, d_feasible);
     if (int rc = sspo::hip_fail(hipGetLastError(), many ? "k_chain_feas query launch" : "k_chain_feas launch")) return rc;
     if (!d_best && !d_best_ctrl) return SSPP_OK;
     hipLaunchKernelGGL(k_chain_best_q, dim3(Q), dim3(kBestBlock), 0, st, d_arc, d_feasible, d_ctrl, (long long)B,
@@ -326,23 +488,24 @@ extern "C" int sspp_chain_sample_score(sspp_chain* c, const double* knots, int d
 // query launch samples every query's candidates and writes their arcs ([Q][B], a batch of Q * B to
 // the feasibility kernel), then one k_chain_best_q workgroup per query.  The job's single-query
 // state, and with it what sspp_chain_sample_score writes, stays as it was.
-extern "C" int sspp_chain_sample_score_queries(sspp_chain* c, const double* knots, int degree, int Q,
-                                               const double* init_ctrl, int n, int W, const double* sigma,
-                                               const double* limits, const uint64_t* seed, int64_t first_id,
-                                               int64_t B, double* d_arc, uint8_t* d_feasible, double* d_ctrl_out,
-                                               sspp_best* d_best, double* d_best_ctrl, void* stream) {
+// (worlds: null, or a worlds launch's [Q][nq]: query q's candidates meet world q)
+static int chain_queries(sspp_chain* c, const std::string& who, const double* knots, int degree, int Q,
+                         const double* init_ctrl, int n, int W, const double* sigma, const double* limits,
+                         const uint64_t* seed, int64_t first_id, int64_t B, double* d_arc, uint8_t* d_feasible,
+                         double* d_ctrl_out, sspp_best* d_best, double* d_best_ctrl, void* stream, bool with_worlds,
+                         const double* worlds) {
     sspp::clear_error();
-    if (!c) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_sample_score_queries: null chain");
-    if (Q < 1 || Q > kChainMaxQueries)
-        return sspp::set_error(SSPP_E_INVAL, "sspp_chain_sample_score_queries: 1..64 queries, got " + std::to_string(Q));
-    if (B < 0) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_sample_score_queries: negative batch");
+    if (!c) return sspp::set_error(SSPP_E_INVAL, who + ": null chain");
+    if (Q < 1 || Q > kChainMaxQueries) return sspp::set_error(SSPP_E_INVAL, who + ": 1..64 queries, got " + std::to_string(Q));
+    if (B < 0) return sspp::set_error(SSPP_E_INVAL, who + ": negative batch");
     if (B == 0) return SSPP_OK;
-    if (!init_ctrl || !sigma || !limits || !seed || !d_arc || !d_feasible)
-        return sspp::set_error(SSPP_E_INVAL, "sspp_chain_sample_score_queries: null argument");
-    if (B > 0x7fffffffll / Q)
-        return sspp::set_error(SSPP_E_INVAL, "sspp_chain_sample_score_queries: too many candidates for one launch");
+    if (!init_ctrl || !sigma || !limits || !seed || !d_arc || !d_feasible || (with_worlds && !worlds))
+        return sspp::set_error(SSPP_E_INVAL, who + ": null argument");
+    if (B > 0x7fffffffll / Q) return sspp::set_error(SSPP_E_INVAL, who + ": too many candidates for one launch");
     int rc;
     if ((rc = chain_job(c, knots, degree, n, W, B))) return rc;
+    WorldTables wt{};
+    if (with_worlds && (rc = chain_stage_worlds(c, who.c_str(), Q, worlds, (hipStream_t)stream, &wt))) return rc;
     if (!d_ctrl_out) {  // the feasibility kernel and the winner gather read the candidates
         const size_t need = (size_t)Q * (size_t)B * n * c->t.D;
         if (need > c->d_qctrl.n) {
@@ -354,7 +517,26 @@ extern "C" int sspp_chain_sample_score_queries(sspp_chain* c, const double* knot
     if ((rc = sspp_job_set_queries(c->job, Q, init_ctrl, sigma, limits, seed, stream)) ||
         (rc = sspp_job_sample_score_queries(c->job, first_id, B, d_arc, d_feasible, d_ctrl_out, c->d_jobbest.p, stream)))
         return rc;
-    return chain_finish(c, d_ctrl_out, first_id, Q, B, d_arc, d_feasible, d_best, d_best_ctrl, true, (hipStream_t)stream);
+    return chain_finish(c, d_ctrl_out, first_id, Q, B, d_arc, d_feasible, d_best, d_best_ctrl, true, (hipStream_t)stream,
+                        with_worlds ? &wt : nullptr);
+}
+
+extern "C" int sspp_chain_sample_score_queries(sspp_chain* c, const double* knots, int degree, int Q,
+                                               const double* init_ctrl, int n, int W, const double* sigma,
+                                               const double* limits, const uint64_t* seed, int64_t first_id,
+                                               int64_t B, double* d_arc, uint8_t* d_feasible, double* d_ctrl_out,
+                                               sspp_best* d_best, double* d_best_ctrl, void* stream) {
+    return chain_queries(c, "sspp_chain_sample_score_queries", knots, degree, Q, init_ctrl, n, W, sigma, limits, seed,
+                         first_id, B, d_arc, d_feasible, d_ctrl_out, d_best, d_best_ctrl, stream, false, nullptr);
+}
+
+extern "C" int sspp_chain_sample_score_worlds(sspp_chain* c, const double* knots, int degree, int Q,
+                                              const double* init_ctrl, int n, int W, const double* sigma,
+                                              const double* limits, const uint64_t* seed, int64_t first_id, int64_t B,
+                                              double* d_arc, uint8_t* d_feasible, double* d_ctrl_out, sspp_best* d_best,
+                                              double* d_best_ctrl, void* stream, const double* worlds) {
+    return chain_queries(c, "sspp_chain_sample_score_worlds", knots, degree, Q, init_ctrl, n, W, sigma, limits, seed,
+                         first_id, B, d_arc, d_feasible, d_ctrl_out, d_best, d_best_ctrl, stream, true, worlds);
 }
 
 // ---- the same on host buffers (the drop-in planner of an articulated model): staged to the device,
@@ -439,13 +621,15 @@ constexpr size_t kChainManyCtrlBytes = (size_t)256 << 20;
 // chunk of at most kChainMaxQueries queries one sspp_chain_sample_score_queries whose k_chain_best_q
 // writes the records and the winners' rows straight into the chain's mapped pinned memory (Q rows;
 // no candidate leaves the device), one stream synchronisation at the end.
-extern "C" int sspp_chain_plan_many_host(sspp_chain* c, int Q, const double* starts, const double* ends, double sigma,
-                                         const double* limits, int sample_count, int check_points, int init_points,
-                                         const uint64_t* seeds, int64_t first_id, double* knots_out,
-                                         sspp_best* best_out, double* best_ctrl_out, int64_t* n_feasible,
-                                         double* arc_out, uint8_t* feasible_out) {
+// (worlds: null, or [Q][nq]: sspp_chain_plan_many_worlds_host, every world validated before the first chunk)
+static int chain_plan_many(sspp_chain* c, int Q, const double* starts, const double* ends, double sigma,
+                           const double* limits, int sample_count, int check_points, int init_points,
+                           const uint64_t* seeds, int64_t first_id, double* knots_out, sspp_best* best_out,
+                           double* best_ctrl_out, int64_t* n_feasible, double* arc_out, uint8_t* feasible_out,
+                           bool with_worlds, const double* worlds) {
     sspp::clear_error();
-    if (!c || !starts || !ends || !limits || !seeds || !knots_out || !best_out || !best_ctrl_out || !n_feasible)
+    if (!c || !starts || !ends || !limits || !seeds || !knots_out || !best_out || !best_ctrl_out || !n_feasible ||
+        (with_worlds && !worlds))
         return sspp::set_error(SSPP_E_INVAL, "sspp_chain_plan_many_host: null argument");
     if (Q < 1) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_plan_many_host: Q must be >= 1");
     const int n = init_points, D = c->t.D, deg = 3;
@@ -454,10 +638,16 @@ extern "C" int sspp_chain_plan_many_host(sspp_chain* c, int Q, const double* sta
         return sspp::set_error(SSPP_E_INVAL, "sspp_chain_plan_many_host: init_points must be >= 4 for a cubic spline");
     if (check_points < 2) return sspp::set_error(SSPP_E_INVAL, "sspp_chain_plan_many_host: check_points must be >= 2");
     // initializePath per query; the knot vector depends on n only
-    const size_t nd = (size_t)n * D;
+    const size_t nd = (size_t)n * D, nq = c->world.size();
     const int64_t B = sample_count;
     std::vector<double> ctrl0((size_t)Q * nd);
     int rc;
+    if (with_worlds) {  // (a bad world in a later chunk must not leave earlier chunks launched)
+        std::vector<double> w;
+        for (int q = 0; q < Q; ++q)
+            if ((rc = chain_world_qpos(c->model, worlds + (size_t)q * nq, (int)nq, "sspp_chain_plan_many_worlds_host", w)))
+                return sspp::set_error(rc, "world " + std::to_string(q) + ": " + sspp_last_error());
+    }
     for (int q = 0; q < Q; ++q)
         if ((rc = sspp::initialize_path(starts + (size_t)q * D, ends + (size_t)q * D, n, D, deg, knots_out,
                                         ctrl0.data() + q * nd)))
@@ -478,9 +668,10 @@ extern "C" int sspp_chain_plan_many_host(sspp_chain* c, int Q, const double* sta
     rc = SSPP_OK;
     for (int q0 = 0; q0 < Q && !rc; q0 += chunk) {
         const int qc = std::min(chunk, Q - q0);
-        rc = sspp_chain_sample_score_queries(c, knots_out, deg, qc, ctrl0.data() + (size_t)q0 * nd, n, check_points,
-                                             sig.data(), lim.data(), seeds + q0, first_id, B, c->dm_arc.p, c->dm_feas.p,
-                                             nullptr, hb + q0, hc + (size_t)q0 * nd, st);
+        rc = chain_queries(c, with_worlds ? "sspp_chain_sample_score_worlds" : "sspp_chain_sample_score_queries", knots_out,
+                           deg, qc, ctrl0.data() + (size_t)q0 * nd, n, check_points, sig.data(), lim.data(), seeds + q0,
+                           first_id, B, c->dm_arc.p, c->dm_feas.p, nullptr, hb + q0, hc + (size_t)q0 * nd, st, with_worlds,
+                           with_worlds ? worlds + (size_t)q0 * nq : nullptr);
         if (!rc && arc_out)
             rc = hip_fail(hipMemcpyAsync(c->hm_arc.p + (size_t)q0 * B, c->dm_arc.p, sizeof(double) * qc * B,
                                          hipMemcpyDeviceToHost, st), "copy arc");
@@ -499,4 +690,23 @@ extern "C" int sspp_chain_plan_many_host(sspp_chain* c, int Q, const double* sta
     if (arc_out) std::memcpy(arc_out, c->hm_arc.p, sizeof(double) * Q * B);
     if (feasible_out) std::memcpy(feasible_out, c->hm_feas.p, (size_t)Q * B);
     return SSPP_OK;
+}
+
+extern "C" int sspp_chain_plan_many_host(sspp_chain* c, int Q, const double* starts, const double* ends, double sigma,
+                                         const double* limits, int sample_count, int check_points, int init_points,
+                                         const uint64_t* seeds, int64_t first_id, double* knots_out,
+                                         sspp_best* best_out, double* best_ctrl_out, int64_t* n_feasible,
+                                         double* arc_out, uint8_t* feasible_out) {
+    return chain_plan_many(c, Q, starts, ends, sigma, limits, sample_count, check_points, init_points, seeds, first_id,
+                           knots_out, best_out, best_ctrl_out, n_feasible, arc_out, feasible_out, false, nullptr);
+}
+
+extern "C" int sspp_chain_plan_many_worlds_host(sspp_chain* c, int Q, const double* starts, const double* ends,
+                                                double sigma, const double* limits, int sample_count, int check_points,
+                                                int init_points, const uint64_t* seeds, int64_t first_id,
+                                                double* knots_out, sspp_best* best_out, double* best_ctrl_out,
+                                                int64_t* n_feasible, double* arc_out, uint8_t* feasible_out,
+                                                const double* worlds) {
+    return chain_plan_many(c, Q, starts, ends, sigma, limits, sample_count, check_points, init_points, seeds, first_id,
+                           knots_out, best_out, best_ctrl_out, n_feasible, arc_out, feasible_out, true, worlds);
 }

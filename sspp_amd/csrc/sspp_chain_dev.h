@@ -70,6 +70,17 @@ struct sspp_chain {
     sspo::Pinned<double> hm_ctrl{hipHostMallocMapped | hipHostMallocCoherent};
     sspo::Pinned<double> hm_arc;
     sspo::Pinned<uint8_t> hm_feas;
+    // worlds (DESIGN.md §5 "Worlds for arms"): the chain's own copy of the model data, which the
+    // updates edit, and its world's qpos (model.qpos0 stays every joint's zero).  A worlds launch:
+    // the Q worlds' body, joint and geom records, staged in pinned memory (bodies | joints | geoms,
+    // each at a 16-byte boundary) and copied into device arrays [Q][nd], [Q][nj], [Q][ng]
+    sspp_model model;
+    std::vector<double> world;
+    int64_t epoch = 0;
+    sspo::Staging wst;
+    sspo::Dev<sspc::CBody> dw_bodies;
+    sspo::Dev<sspc::CJoint> dw_joints;
+    sspo::Dev<sspc::CGeom> dw_geoms;
     ~sspp_chain() {
         if (job) sspp_job_free(job);
     }

@@ -352,6 +352,43 @@ class Chain:
         check(lib().sspp_chain_static_pairs(self._h, infos, c, d, n.value, C.byref(n)), "chain static pairs")
         return _pair_dicts(self.model, infos[:n.value], c, d)
 
+    # Worlds (sspp_chain_set_qpos / _set_body_pose, DESIGN.md §5 "Worlds for arms"): what the pose
+    # rule does not drive.  Host-synchronous; no launch that uses the chain may be in flight on the
+    # caller's streams.  Every call afterwards reads the new world; nothing is allocated.
+    def set_qpos(self, qpos):
+        """The world's qpos [nq] in the model's layout: frozen joints' values, frozen free bodies'
+        poses (entries below dof are stored and never read)."""
+        q = _f64(qpos)
+        check(lib().sspp_chain_set_qpos(self._h, _dptr(q), int(q.size)), "chain set_qpos")
+
+    def set_body_pose(self, body, pos, quat):
+        """One body (id or name): a free body's 7 qpos, or any other body's pos / quat relative to
+        its parent (a body of the driven chain included); children follow."""
+        if isinstance(body, str):
+            body = self.model.body_id(body)
+        p, q = _f64(pos, 3), _f64(quat, 4)
+        check(lib().sspp_chain_set_body_pose(self._h, int(body), _dptr(p), _dptr(q)), "chain set_body_pose")
+
+    def get_qpos(self):
+        nq = int(self.model.arrays()["qpos0"].size)
+        out = np.zeros(nq)
+        check(lib().sspp_chain_get_qpos(self._h, _dptr(out), nq), "chain qpos")
+        return out
+
+    @property
+    def epoch(self):
+        v = C.c_int64()
+        check(lib().sspp_chain_epoch(self._h, C.byref(v)), "chain epoch")
+        return int(v.value)
+
+    def _worlds(self, worlds, Q):
+        """worlds (Q, nq) as a contiguous float64 array"""
+        nq = int(self.model.arrays()["qpos0"].size)
+        w = np.ascontiguousarray(np.asarray(worlds, dtype=np.float64))
+        if w.shape != (Q, nq):
+            raise ValueError("worlds must be (%d, %d), got %s" % (Q, nq, w.shape))
+        return w
+
     def _poses(self, q):
         torch = _torch()
         if not (hasattr(q, "is_cuda") and q.is_cuda):
@@ -459,11 +496,13 @@ class Chain:
               "chain sample_score")
 
     def sample_score_queries(self, knots, degree, init_ctrl, sigma, limits, seeds, check_points, first_id, B, arc,
-                             feasible, best=None, ctrl_out=None, best_ctrl=None, stream=None):
+                             feasible, best=None, ctrl_out=None, best_ctrl=None, stream=None, worlds=None):
         """Q queries in one launch sequence (sspp_chain_sample_score_queries): init_ctrl (Q, n, dof),
         sigma (Q,), limits (Q, dof), seeds (Q,).  Row q of the device tensors arc / feasible (Q, B),
         ctrl_out (Q, B, n, dof), best (Q, 4) and best_ctrl (Q, n, dof, the winner's control points,
-        zeros without one) is what sample_score writes for query q alone.  Asynchronous."""
+        zeros without one) is what sample_score writes for query q alone.  Asynchronous.
+        worlds (Q, nq): query q is scored in the chain's world with its qpos replaced by worlds[q]
+        (sspp_chain_sample_score_worlds): row q is what sample_score writes after set_qpos(worlds[q])."""
         knots = _f64(knots)
         init_ctrl = np.ascontiguousarray(np.asarray(init_ctrl, dtype=np.float64))
         if init_ctrl.ndim != 3 or init_ctrl.shape[2] != self.dof:
@@ -477,6 +516,15 @@ class Chain:
                                                 dtype=np.uint64))
         if seeds.size != Q:
             raise ValueError("expected %d seeds, got %d" % (Q, seeds.size))
+        if worlds is not None:
+            w = self._worlds(worlds, Q)
+            check(lib().sspp_chain_sample_score_worlds(self._h, _dptr(knots), int(degree), Q, _dptr(init_ctrl), n,
+                                                       int(check_points), _dptr(sigma), _dptr(limits),
+                                                       seeds.ctypes.data_as(C.POINTER(C.c_uint64)), int(first_id), int(B),
+                                                       _ptr(arc), _ptr(feasible), _ptr(ctrl_out), _ptr(best),
+                                                       _ptr(best_ctrl), _stream(stream), _dptr(w)),
+                  "chain sample_score_worlds")
+            return
         check(lib().sspp_chain_sample_score_queries(self._h, _dptr(knots), int(degree), Q, _dptr(init_ctrl), n,
                                                     int(check_points), _dptr(sigma), _dptr(limits),
                                                     seeds.ctypes.data_as(C.POINTER(C.c_uint64)), int(first_id), int(B),
@@ -484,12 +532,14 @@ class Chain:
                                                     _ptr(best_ctrl), _stream(stream)), "chain sample_score_queries")
 
     def plan_many(self, starts, ends, sigma, limits, sample_count, check_points, init_points, seeds=None, first_id=0,
-                  return_all=False):
+                  return_all=False, worlds=None):
         """SamplingPathPlanner::plan for Q queries of this arm in one call (sspp_chain_plan_many_host):
         starts / ends (Q, dof); sigma, limits and the shape are shared; seeds (Q,), DEFAULT_SEED each
         when None.  Returns dict(knots, best = Q tuples (cost, index, count), best_ctrl (Q, n, dof),
         n_feasible (Q,)), with return_all also arc (Q, sample_count) and feasible (Q, sample_count).
-        Query q's record and winner row are those of a plan of (starts[q], ends[q], seeds[q]) alone."""
+        Query q's record and winner row are those of a plan of (starts[q], ends[q], seeds[q]) alone.
+        worlds (Q, nq): query q is planned in the chain's world with its qpos replaced by worlds[q]
+        (sspp_chain_plan_many_worlds_host): as a plan after set_qpos(worlds[q])."""
         starts = np.ascontiguousarray(np.asarray(starts, dtype=np.float64))
         ends = np.ascontiguousarray(np.asarray(ends, dtype=np.float64))
         if starts.ndim != 2 or starts.shape[1] != self.dof or ends.shape != starts.shape:
@@ -506,11 +556,15 @@ class Chain:
         nf = np.zeros(max(Q, 1), dtype=np.int64)
         arc = np.zeros((Q, max(B, 0))) if return_all else None
         feas = np.zeros((Q, max(B, 0)), dtype=np.uint8) if return_all else None
-        check(lib().sspp_chain_plan_many_host(
-            self._h, Q, _dptr(starts), _dptr(ends), float(sigma), _dptr(lim), B, int(check_points), n,
-            seeds.ctypes.data_as(C.POINTER(C.c_uint64)), int(first_id), _dptr(knots), best, _dptr(best_ctrl),
-            nf.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(arc) if return_all else None,
-            feas.ctypes.data_as(C.POINTER(C.c_uint8)) if return_all else None), "chain plan_many")
+        args = (self._h, Q, _dptr(starts), _dptr(ends), float(sigma), _dptr(lim), B, int(check_points), n,
+                seeds.ctypes.data_as(C.POINTER(C.c_uint64)), int(first_id), _dptr(knots), best, _dptr(best_ctrl),
+                nf.ctypes.data_as(C.POINTER(C.c_int64)), _dptr(arc) if return_all else None,
+                feas.ctypes.data_as(C.POINTER(C.c_uint8)) if return_all else None)
+        if worlds is not None:
+            w = self._worlds(worlds, Q)
+            check(lib().sspp_chain_plan_many_worlds_host(*args, _dptr(w)), "chain plan_many (worlds)")
+        else:
+            check(lib().sspp_chain_plan_many_host(*args), "chain plan_many")
         out = dict(knots=knots, best=[(float(b.cost), int(b.index), int(b.count)) for b in best[:Q]], best_ctrl=best_ctrl,
                    n_feasible=nf[:Q].copy())
         if return_all:
